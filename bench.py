@@ -1,16 +1,26 @@
 """Headline benchmark: gradient updates/sec of the REDQ critic update (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--critics N] [--obs S] [--act A] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--repeats R]] [--critics N] [--obs S]
+                    [--act A] [--batch B]
 
 One "step" = one ``learning.critic_update`` call on a synthetic replay batch (obs 17, act 6, batch 512, N=10 critics,
 n=2 target subset, hidden 256, fp32 -- the shape the metric is quoted on) followed, every ``target_delay``=2 updates,
 by the Polyak update of the target critics, exactly as the reference's UTD loop does (main.py:379-414).  The replay
 buffer (100k transitions) is resident in HBM before the timed region starts; the per-update host work that remains
 (index draw from the torch CPU generator, REDQ subset draw, a 4 KB index upload) is part of the path and is inside the
-timed region.  After W untimed warm-up steps, EXACTLY K steps are timed between barrier + synchronize brackets; this is
-done R times (default 31: at the driver's K = 20 that is ~35 ms, past the ~14 ms the core clock takes to ramp after the idle
-construction phase; every repeat's time and the shader clock beside it are listed in the line) and the MEDIAN repeat is
-reported (``value`` = K / median seconds).
+timed region.  After W untimed warm-up steps, EXACTLY K steps are timed between barrier + synchronize brackets
+(``value`` = K / seconds, ``ms_per_step`` = milliseconds per step).  A plain run does only that: set-up, warm-up, the K
+timed steps, the output dump when asked for, the result line.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the arrays a caller of critic_update
+receives (TD targets, the drawn replay indices and REDQ subset, every scalar log) and the critic / target-critic
+parameters it leaves behind -- is written as DIR/<name>.npy (float32 / float64, a few MB).  Inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+--full: everything beyond the headline figure as well -- the timed region is done R times (--repeats, default 31 under
+--full: at the driver's K = 20 that is ~35 ms, past the ~14 ms the core clock takes to ramp after the idle construction
+phase; every repeat's time and the shader clock beside it are listed in the line) and the MEDIAN repeat is reported
+(SURVEY 8(d)), followed by the roofline of the dominant kernel, the CPU baseline and the secondary rows.
 
 --critics / --obs / --act / --batch (defaults 10 / 17 / 6 / 512 = the headline) select another ensemble: `--gpus 8
 --critics 16` is the configuration BASELINE.json's scaling target is quoted on (N = 16 critics over 8 GPUs), `--obs 376
@@ -22,8 +32,9 @@ starts the N ranks itself as child processes and relays rank 0's line.  The crit
 ranks (super_sac_amd.parallel); the one exchange per update (MIN of the per-shard subset min-Q) is a recorded launch
 of the one-shot IPC exchange kernel (csrc/ssac_xchg.hip), RCCL being the fallback.  Total work is fixed: "strong".
 
-Prints ONE JSON line (rank 0) with `roofline` for the dominant kernel, `cpu_baseline` (the CPU oracle -- a port of the
-reference's update -- timed on this host's cores) and `secondary` rows (full REDQ environment step; bf16 config 2).
+Prints ONE JSON line (rank 0); under --full it also carries `roofline` for the dominant kernel, `cpu_baseline` (the CPU
+oracle -- a port of the reference's update -- timed on this host's cores) and `secondary` rows (full REDQ environment
+step; bf16 config 2).
 """
 import argparse
 import copy
@@ -182,6 +193,7 @@ def build_engine(device, n_local, shard=None, batch=None, precision="fp32", obs=
             for ac, tc in zip(agent.critics, target.critics):
                 ssa.learning_utils.soft_update(tc, ac, TAU)
         state["k"] += 1
+        state["dicts"] = dicts
         return dicts
 
     def env_step():
@@ -336,6 +348,10 @@ def launch_ranks(args):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--critics", str(args.critics),
                "--obs", str(args.obs), "--act", str(args.act), "--batch", str(args.batch)]
+        if args.full:
+            cmd.append("--full")
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", args.dump_outputs]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.no_secondary:
@@ -376,13 +392,120 @@ def timed_repeats(fn, steps, repeats, dist, device, clocks=None):
     return times
 
 
+def dump_outputs(out_dir, step, device, limit_bytes=64 << 20):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy -- the arrays critic_update hands its caller
+    (the replay dict: batch, TD targets, indices, REDQ subset; every scalar log) and the parameters the step leaves behind
+    (critics and Polyak targets of this rank), float32 (float64 for integers and logs)"""
+    import re
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    ob = step.objects
+    arrays = {}
+
+    def put(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                put(f"{name}_{k}", x)
+            return
+        if isinstance(v, (list, tuple)) and not all(isinstance(x, (bool, int, float, np.number)) for x in v):
+            for i, x in enumerate(v):
+                put(f"{name}_{i}", x)
+            return
+        if torch.is_tensor(v):
+            v = v.detach().float().cpu().numpy() if v.dtype in (torch.float16, torch.bfloat16) else v.detach().cpu().numpy()
+        elif isinstance(v, (list, tuple)):
+            v = np.asarray(v)
+        if isinstance(v, np.ndarray) and v.dtype.kind in "biuf":
+            keep = np.float64 if v.dtype.kind in "iu" or v.dtype == np.float64 else np.float32
+            arrays[re.sub(r"[^0-9A-Za-z]+", "_", name).strip("_")] = np.ascontiguousarray(v, dtype=keep)
+    for k, v in ob["state"]["dicts"][0].items():
+        put(k, v)
+    for k, v in ob["state"]["logs"].items():
+        put("log_" + k, np.array([float(v)], np.float64))
+    put("critic_params", ob["agent"].critics[0].arena(device).params)
+    put("target_critic_params", ob["target"].critics[0].arena(device).params)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= limit_bytes, f"--dump-outputs: {total} bytes over the {limit_bytes} byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def full_roofline(args, ssa, step, n_local, world, headline):
+    """--full: the roofline of the dominant kernel, from an eager pass with HIP events after the timed region"""
+    # ---- roofline of the dominant kernel: the chained launch (ensemble-Q forward + TD-independent backward of all local
+    # critics beside the target chains).  Algorithmic FLOPs per launch (SURVEY 8(d)): 2*B*N*(in*H + H*H + H) for the
+    # critics' forward, 2*B*N*(H + H*H) for their backward-data, the target critics of the subset and the actor once
+    # (round 4: the launch's producer / consumer form runs the actor once per tile -- executed = algorithmic).  The timed
+    # region re-issues the
+    # update from ONE recorded launch list, inside which a single kernel is not bracketed by events; so the same
+    # update is run again right here with plain launches and the launch is bracketed by HIP events recorded on the
+    # stream it is launched on (same shapes, buffers, binary), 8 back-to-back issues per event pair.
+    import torch
+    graphs_were_on = ssa.learning.USE_GRAPHS
+    ssa.learning.USE_GRAPHS = False
+    ssa.engine.PROFILE["tag"] = ("critic_fwd", "critic_bwd", "critic_fused", "dual_fwd", "dual_bwd", "chain")
+    ssa.engine.PROFILE["events"] = []
+    ssa.engine.PROFILE["reps"] = 8
+    for _ in range(min(args.steps, 300)):
+        step()
+    torch.cuda.synchronize()
+    ssa.engine.PROFILE["tag"] = None
+    ssa.engine.PROFILE["reps"] = 1
+    ssa.learning.USE_GRAPHS = graphs_were_on
+    by_tag = {}
+    for a, b, tag, reps in ssa.engine.PROFILE["events"]:
+        by_tag.setdefault(tag, []).append(a.elapsed_time(b) / reps)
+    IN = OBS + ACT
+    f_fwd = 2.0 * BATCH * n_local * (IN * HID + HID * HID + HID)
+    f_bwd = 2.0 * BATCH * n_local * (HID + HID * HID)
+    f_actor = 2.0 * BATCH * (OBS * HID + HID * HID + HID * 2 * ACT)
+    f_tgt = 2.0 * BATCH * NSUB * (IN * HID + HID * HID + HID)
+    if "chain" in by_tag:
+        ms = by_tag["chain"]
+        flops, kname = f_fwd + f_bwd + f_tgt + f_actor, (
+            "fused_chain_pc_kernel: ensemble-Q forward (fc1+fc2+head, h1/h2/q saved) AND the TD-independent half of the "
+            "backward pass (head backward + fc2 backward-data) of all local critics as 32-row workgroups, beside the "
+            "target chains as producer / consumer workgroups of 16 rows (the actor forward + tanh-normal sample once per "
+            "tile hands a' to the tile's target critics of the REDQ subset, which have run fc1 on the state columns "
+            "meanwhile); every workgroup gathers its own replay rows; ONE launch per update")
+    elif "dual_fwd" in by_tag:
+        ms = by_tag["dual_fwd"]
+        flops, kname = f_fwd + f_actor, "fused_dual_kernel: ensemble-Q forward + actor forward/sample, ONE launch"
+    elif "critic_fwd" in by_tag:
+        ms = by_tag["critic_fwd"]
+        flops, kname = f_fwd, "fused_mlp_kernel<plain>: ensemble-Q forward (fc1+fc2+head) of all local critics"
+    else:
+        ms = by_tag["critic_fused"]
+        flops, kname = f_fwd + f_bwd, "fused_mlp_kernel<critic>: forward + loss gradient + backward-data, ONE launch"
+    avg_ms = sum(ms) / len(ms)
+    achieved = flops / (avg_ms * 1e-3) / 1e12
+    single = world == 1 and n_local == NCRIT and "chain" in by_tag and headline
+    roofline = {"kernel": kname, "bound": "mfma", "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+                "avg_launch_us": round(avg_ms * 1e3, 3), "launches_timed": len(ms),
+                "timing": "HIP events on the launch stream around 8 back-to-back issues of the (idempotent) launch, "
+                          "in an eager pass right after the timed (replayed) region",
+                "flops_per_launch": flops,
+                "traffic": None, "traffic_source": None}
+    if single:
+        roofline["traffic"], roofline["traffic_source"] = recorded_traffic()
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=31,
-                    help="timed regions of EXACTLY --steps steps each (every one listed in the line); the median is the value")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of EXACTLY --steps steps each (every one listed in the line); the median is the value "
+                         "(default 1; 31 under --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeated timed regions, the roofline pass, the CPU baseline and the secondary rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--interrupt-wait", action="store_true",
                     help="keep the ROCm runtime's interrupt-driven host waits (default here: polling, HSA_ENABLE_INTERRUPT=0)")
@@ -392,6 +515,8 @@ def main():
     ap.add_argument("--act", type=int, default=ACT, help="action size (17: Humanoid)")
     ap.add_argument("--batch", type=int, default=BATCH)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 31 if args.full else 1
     headline = (args.critics, args.obs, args.act, args.batch) == (10, 17, 6, 512)
     globals().update(NCRIT=args.critics, OBS=args.obs, ACT=args.act, BATCH=args.batch)   # (read by every helper below)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -487,63 +612,10 @@ def main():
         from super_sac_amd import parallel
         if parallel.exchange_failed():   # a peer's flag never arrived: the numbers above would be of a broken run
             raise RuntimeError("one-shot exchange: a peer's flag did not arrive within the spin limit")
-
-    # ---- roofline of the dominant kernel: the chained launch (ensemble-Q forward + TD-independent backward of all local
-    # critics beside the target chains).  Algorithmic FLOPs per launch: 2*B*N*(in*H + H*H + H) for the
-    # critics' forward, 2*B*N*(H + H*H) for their backward-data, the target critics of the subset and the actor once
-    # (round 4: the launch's producer / consumer form runs the actor once per tile -- executed = algorithmic).  The timed
-    # region re-issues the
-    # update from ONE recorded launch list, inside which a single kernel is not bracketed by events; so the same
-    # update is run again right here with plain launches and the launch is bracketed by HIP events recorded on the
-    # stream it is launched on (same shapes, buffers, binary), 8 back-to-back issues per event pair.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, device)
     graphs_were_on = ssa.learning.USE_GRAPHS
-    ssa.learning.USE_GRAPHS = False
-    ssa.engine.PROFILE["tag"] = ("critic_fwd", "critic_bwd", "critic_fused", "dual_fwd", "dual_bwd", "chain")
-    ssa.engine.PROFILE["events"] = []
-    ssa.engine.PROFILE["reps"] = 8
-    for _ in range(min(args.steps, 300)):
-        step()
-    torch.cuda.synchronize()
-    ssa.engine.PROFILE["tag"] = None
-    ssa.engine.PROFILE["reps"] = 1
-    ssa.learning.USE_GRAPHS = graphs_were_on
-    by_tag = {}
-    for a, b, tag, reps in ssa.engine.PROFILE["events"]:
-        by_tag.setdefault(tag, []).append(a.elapsed_time(b) / reps)
-    IN = OBS + ACT
-    f_fwd = 2.0 * BATCH * n_local * (IN * HID + HID * HID + HID)
-    f_bwd = 2.0 * BATCH * n_local * (HID + HID * HID)
-    f_actor = 2.0 * BATCH * (OBS * HID + HID * HID + HID * 2 * ACT)
-    f_tgt = 2.0 * BATCH * NSUB * (IN * HID + HID * HID + HID)
-    if "chain" in by_tag:
-        ms = by_tag["chain"]
-        flops, kname = f_fwd + f_bwd + f_tgt + f_actor, (
-            "fused_chain_pc_kernel: ensemble-Q forward (fc1+fc2+head, h1/h2/q saved) AND the TD-independent half of the "
-            "backward pass (head backward + fc2 backward-data) of all local critics as 32-row workgroups, beside the "
-            "target chains as producer / consumer workgroups of 16 rows (the actor forward + tanh-normal sample once per "
-            "tile hands a' to the tile's target critics of the REDQ subset, which have run fc1 on the state columns "
-            "meanwhile); every workgroup gathers its own replay rows; ONE launch per update")
-    elif "dual_fwd" in by_tag:
-        ms = by_tag["dual_fwd"]
-        flops, kname = f_fwd + f_actor, "fused_dual_kernel: ensemble-Q forward + actor forward/sample, ONE launch"
-    elif "critic_fwd" in by_tag:
-        ms = by_tag["critic_fwd"]
-        flops, kname = f_fwd, "fused_mlp_kernel<plain>: ensemble-Q forward (fc1+fc2+head) of all local critics"
-    else:
-        ms = by_tag["critic_fused"]
-        flops, kname = f_fwd + f_bwd, "fused_mlp_kernel<critic>: forward + loss gradient + backward-data, ONE launch"
-    avg_ms = sum(ms) / len(ms)
-    achieved = flops / (avg_ms * 1e-3) / 1e12
-    single = world == 1 and n_local == NCRIT and "chain" in by_tag and headline
-    roofline = {"kernel": kname, "bound": "mfma", "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                "avg_launch_us": round(avg_ms * 1e3, 3), "launches_timed": len(ms),
-                "timing": "HIP events on the launch stream around 8 back-to-back issues of the (idempotent) launch, "
-                          "in an eager pass right after the timed (replayed) region",
-                "flops_per_launch": flops,
-                "traffic": None, "traffic_source": None}
-    if single:
-        roofline["traffic"], roofline["traffic_source"] = recorded_traffic()
+    roofline = full_roofline(args, ssa, step, n_local, world, headline) if args.full else None
 
     if rank == 0:
         out = {"metric": f"gradient updates/sec (REDQ N={NCRIT}, batch {BATCH})", "value": round(args.steps / dt, 2),
@@ -565,12 +637,13 @@ def main():
                           "parallelism": "single GPU" if world == 1 else
                                          f"critic-ensemble sharded x{world}" +
                                          (f" ({world} ranks sharing {ndev} device(s))" if shared_device else ""),
-                          "exchange": exchange},
-               "roofline": roofline}
+                          "exchange": exchange}}
+        if roofline is not None:
+            out["roofline"] = roofline
         if value_check is not None:
             out["sharded_value_check"] = value_check
     secondary = {}
-    if not args.no_secondary and world == 1:
+    if args.full and not args.no_secondary and world == 1:
         try:   # (a failing secondary row must not cost the headline line)
             # ---- full REDQ environment step (SURVEY 8(d) secondary unit): 20 critic updates + 10 Polyak + actor + alpha
             for _ in range(3):
@@ -631,7 +704,7 @@ def main():
     if rank == 0:
         if secondary:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:   # noqa: BLE001  (the GPU numbers above are still worth a line)

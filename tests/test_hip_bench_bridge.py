@@ -59,8 +59,18 @@ def _mlp_dict(mod, head):
     return {"w1": w1, "b1": b1, "w2": w2, "b2": b2, "w3": w3, "b3": b3}
 
 
+def _load_mlp(mod, head, w):
+    for lin, k in ((mod.fc1, "1"), (mod.fc2, "2"), (getattr(mod, head), "3")):
+        lin.weight.copy_(w["w" + k])
+        lin.bias.copy_(w["b" + k])
+
+
 def _engine_run(sync_every_update):
-    """bench.build_engine's step closure, N_UPDATES times; returns everything the comparison needs"""
+    """bench.build_engine's step closure, N_UPDATES times; returns everything the comparison needs.  The initial weights
+    are the oracle's seeded numpy draws (ssac_oracle.make_mlp: the same values on every host), written over the closure's
+    orthogonal initialisation before its first update: that one comes out of the host's LAPACK QR, whose results differ
+    from one machine's math library to another's, and which ReLU units sit on a rounding boundary in some update -- what
+    this comparison can tolerate -- must not depend on the machine the suite runs on."""
     import bench
     import super_sac_amd as ssa
     from super_sac_amd import learning_utils as lu
@@ -68,6 +78,13 @@ def _engine_run(sync_every_update):
     step, _, _ = bench.build_engine(dev, bench.NCRIT)
     ob = step.objects
     agent, target = ob["agent"], ob["target"]
+    seeded = orc.AgentOracle(state_dim=bench.OBS, act_dim=bench.ACT, hidden=bench.HID, num_critics=bench.NCRIT, seed=0)
+    with torch.no_grad():
+        _load_mlp(agent.actors[0], "fc3", seeded.actors[0])
+        _load_mlp(target.actors[0], "fc3", seeded.actors[0])
+        for net, tnet, w in zip(agent.critics[0].nets, target.critics[0].nets, seeded.critics[0]):
+            _load_mlp(net, "out", w)
+            _load_mlp(tnet, "out", w)
     assert ssa.rng.normal_is_stock() and ssa.learning.LAUNCH_MODE == "list" and ssa.learning.USE_GRAPHS
     init = dict(actor=_mlp_dict(agent.actors[0], "fc3"),
                 critics=[_mlp_dict(n, "out") for n in agent.critics[0].nets],

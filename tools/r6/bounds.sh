@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r6/bounds; mkdir -p $O
 run() {  # tag
   for rep in 1 2; do
-    SSAC_LAB_BUILD=1 SSAC_LAB_TAG=$1 timeout 200 python bench.py --steps 2000 --warmup 300 --repeats 5 --no-cpu-baseline --no-secondary 2>/dev/null |
+    SSAC_LAB_BUILD=1 SSAC_LAB_TAG=$1 timeout 200 python bench.py --full --steps 2000 --warmup 300 --repeats 5 --no-cpu-baseline --no-secondary 2>/dev/null |
       python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1'.ljust(8) or 'base', 'us/update', round(1e3*d['ms_per_step'],2), 'min', round(1e3*d['ms_per_step_min'],2), 'chained launch us', d['roofline']['avg_launch_us'])"
   done
 }
