@@ -587,6 +587,40 @@ int ssac_det_action_bwd(const float *dX, int n_nets, int64_t ldx, int64_t x_net_
                         int64_t act_col0, const float *out, int64_t ld_out, int n_rows, int act_dim,
                         float *d_out, int64_t ld_dout, void *stream);
 
+/* ---- Beta policy head (Agent(beta_dist=True): distributions.py:18-53; csrc/ssac_beta.hip).
+ * vec (n_rows x 2A, row stride ld_vec) is the actor head output, laid out as for the tanh-normal head:
+ *   alpha = 1 + softplus(vec[:, :A]), beta = 1 + softplus(vec[:, A:])   (threshold 20, fp32)
+ *   log pi_b = sum_i xlogy(alpha-1, x) + xlogy(beta-1, 1-x) + lgamma(alpha+beta) - lgamma(alpha) - lgamma(beta) - log 2
+ * (1 - x in fp32; lgamma / digamma / the reparameterisation gradient in fp64).
+ * ssac_beta_fwd modes:
+ *   SSAC_BETA_SAMPLE  x ~ Beta(alpha, beta): x_in (row stride ld_x_in) when not NULL, else drawn from `rng`'s Philox
+ *                     stream (Marsaglia-Tsang Gamma pair, x = G1 / (G1 + G2), keyed by (row, column, draw number
+ *                     offset + *counter, attempt); at most 32 attempts per Gamma, then the fallback shape - 1/3).  A
+ *                     drawn x is nudged into [FLT_MIN, 1 - 2^-24].  a = 2x - 1 -> act_dst[b * ld_act + act_col0 + i]
+ *                     (nullable), x -> x_save (n_rows x A, nullable), log pi -> logp (n_rows, nullable; per-row sum
+ *                     in a fixed order).
+ *   SSAC_BETA_MEAN    act_dst = 2 alpha / (alpha + beta) - 1 (the distribution's mean); nothing else is written.
+ *   SSAC_BETA_GIVEN   x_in holds ACTIONS (row stride ld_x_in): x = (clamp(a, -0.99, 0.99) + 1) / 2 (the transform's
+ *                     inverse); log pi -> logp, x -> x_save.  act_dst is not written.
+ * act_dim <= 256. */
+#define SSAC_BETA_SAMPLE 0
+#define SSAC_BETA_MEAN 1
+#define SSAC_BETA_GIVEN 2
+int ssac_beta_fwd(const float *vec, int64_t ld_vec, int n_rows, int act_dim, int mode, const float *x_in,
+                  int64_t ld_x_in, const ssac_rng *rng, float *act_dst, int64_t ld_act, int64_t act_col0,
+                  float *logp, float *x_save, void *stream);
+/* backward of the Beta head: d_vec (n_rows x 2A, row stride ld_dvec) = dL/d vec.
+ * data_action == 0 (a sampled action, actor loss): dL/da = sum_j dX_j[:, act_col0 + i] as in ssac_tanh_normal_bwd,
+ *   dL/d log pi_b = exp(*log_alpha) * inv_members / n_rows when use_entropy (else 0); the gradient reaches the
+ *   concentrations through x (torch's _Dirichlet_backward with torch._dirichlet_grad, ported from ATen) and directly
+ *   through the log-density (digamma terms), then through softplus.
+ * data_action != 0 (x fixed, behavioural cloning): dX / log_alpha / use_entropy unused; dL/d log pi_b = inv_members / n_rows
+ *   (pass -1/E for the loss -mean(log pi) / E).
+ * x_saved: the x of ssac_beta_fwd (its x_save). */
+int ssac_beta_bwd(const float *dX, int n_nets, int64_t ldx, int64_t x_net_stride, int64_t act_col0, const float *vec,
+                  int64_t ld_vec, const float *x_saved, int n_rows, int act_dim, const float *log_alpha, int use_entropy,
+                  float inv_members, int data_action, float *d_vec, int64_t ld_dvec, void *stream);
+
 /* ---- SAC-Discrete actor loss gradient: learning.py:382-390,407-408.
  * logits (n_rows x A); q (n_nets x n_rows x A) elementwise min (agent.py:38), no grad.
  * loss = -(1/E) mean_b sum_a pi (minq' - alpha log pi);  d_logits written. */

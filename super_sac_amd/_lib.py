@@ -171,6 +171,8 @@ SIGNATURES = {
     "ssac_actor_loss_bwd_adv": [_P, _I, _I, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P],
     "ssac_tanh_normal_bwd": [_P, _I, _L, _L, _L, _P, _L, _P, _I, _I, _F, _F, _P, _I, _F, _P, _L, _P],
     "ssac_det_action_bwd": [_P, _I, _L, _L, _L, _P, _L, _I, _I, _P, _L, _P],
+    "ssac_beta_fwd": [_P, _L, _I, _I, _I, _P, _L, _P, _P, _L, _L, _P, _P, _P],
+    "ssac_beta_bwd": [_P, _I, _L, _L, _L, _P, _L, _P, _I, _I, _P, _I, _F, _I, _P, _L, _P],
     "ssac_discrete_actor_loss_bwd": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P],
     "ssac_alpha_update": [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
     "ssac_sunrise_weights": [_P, _I, _I, _F, _P, _P, _P],

@@ -10,7 +10,7 @@ no hipMemcpy, no stream synchronisation.  Measured (bench.py ``secondary.acting`
 
 What stays on the general path (agent.py's eager code, unchanged): pixel encoders, injected noise (a hook on
 ``rng.draw_normal`` -- the parity tests), discrete UCB, networks outside the fused kernels' shapes (hidden > 256),
-``from_cpu=False`` callers.  Host RNG contract: the Python ``random`` draws of the reference (``random.choice`` of the
+``from_cpu=False`` callers, Beta actors (beta_dist=True).  Host RNG contract: the Python ``random`` draws of the reference (``random.choice`` of the
 acting actor / of the logged distribution) are consumed exactly as before."""
 import ctypes as C
 import weakref
@@ -119,6 +119,8 @@ def _eligible(agent, obs, num_envs, sample, rolling):
     if E > 8 or agent.act_space_size > 64:
         return False
     kind = lu.actor_kind(agent.actors[0])
+    if kind == "beta":
+        return False          # (the recorded rules sample the tanh-normal head: Beta actors act on the general path)
     if sample and kind == "stochastic" and not rng.normal_is_stock():
         return False          # injected noise: the general path draws it through the hook
     if sample and agent.ucb_bonus > 0 and (agent.discrete or kind != "stochastic" or E < 2):

@@ -63,6 +63,9 @@ class AdvantageEstimator:
             return res
         A = actor.action_size
         n = N_SAMPLES
+        if lu.actor_kind(actor) == "beta":
+            raise NotImplementedError("AdvantageEstimator (advantage filter, PER refresh, use_baseline): Beta policies "
+                                      "(beta_dist=True) are not supported here")
         # stacked batch: block 0 = (s, a_data), blocks 1..n = (s, a_k)
         X = ws.get(f"adv.x{i}", ((n + 1) * B, S + A))
         Xv = X.view(n + 1, B, S + A)

@@ -8,7 +8,7 @@ import os
 import torch
 from torch import nn
 
-from . import engine, nets, popart, rng
+from . import beta, engine, nets, popart, rng
 from . import device as _default_device
 
 
@@ -52,13 +52,12 @@ class Agent:
                  auto_rescale_targets=True, log_std_low=-10.0, log_std_high=2.0, adv_method=None,
                  beta_dist=False):
         assert hasattr(encoder, "embedding_dim")
-        assert not beta_dist, "Beta policies are outside the accelerated path"
         actor_kwargs = {"state_size": encoder.embedding_dim, "action_size": act_space_size,
                         "hidden_size": hidden_size}
         critic_kwargs = dict(actor_kwargs)
         if not discrete:
             actor_kwargs.update({"log_std_low": log_std_low, "log_std_high": log_std_high,
-                                 "dist_impl": "pyd"})
+                                 "dist_impl": "beta" if beta_dist else "pyd"})
         self.encoder = encoder
         self.actors = [actor_network_cls(**actor_kwargs) for _ in range(ensemble_size)]
         self.critics = [Critic(critic_network_cls, critic_kwargs, num_critics)
@@ -134,10 +133,13 @@ class Agent:
 
     def _mean_action(self, actor, out):
         """dist.mean of a continuous actor: tanh(mu) (SquashedNormal.mean, distributions.py:99-104) or the
-        deterministic actor's tanh(out) (mlps.py:91-92), by the det-action kernel without noise."""
+        deterministic actor's tanh(out) (mlps.py:91-92), by the det-action kernel without noise; a Beta actor's
+        2 alpha / (alpha + beta) - 1 by its head kernel."""
         from ._lib import check, lib
         n, A = out.shape[0], actor.action_size
         act = torch.empty(n, A, device=out.device)
+        if getattr(actor, "dist_impl", None) == "beta":
+            return beta.mean_into(out, n, A, act)  # BetaDist.mean = 2 alpha / (alpha + beta) - 1 (distributions.py:51-56)
         check(lib.ssac_det_action_fwd(out.data_ptr(), out.shape[1], 0, 0.0, 0, 0.0, 0.0, n, A,
                                       act.data_ptr(), A, 0, engine.stream()))
         return act
@@ -152,6 +154,10 @@ class Agent:
         act = torch.empty(n, A, device=out.device)
         if getattr(actor, "dist_impl", None) == "deterministic":
             return self._mean_action(actor, out)  # ContinuousDeterministic.sample() = loc
+        if getattr(actor, "dist_impl", None) == "beta":
+            # BetaDist.sample(): x from the agent's engine stream (acting site) or the rng.draw_beta_into hook
+            beta.sample(self, out, n, A, "act", torch.empty(n, A, device=out.device), act, A, 0)
+            return act
         eps = rng.draw_normal((n, A), out.device)
         check(lib.ssac_tanh_normal_fwd(out.data_ptr(), 2 * A, eps.data_ptr(), n, A, float(actor.log_std_low),
                                        float(actor.log_std_high), act.data_ptr(), A, 0, 0, engine.stream()))

@@ -269,6 +269,8 @@ def set_precision(agent, precision):
     default) or "bf16" (BASELINE.json config 2; fp32 masters + bf16 shadows, csrc/ssac_bf16.hip).  Marks the modules, so
     a later ``copy.deepcopy(agent)`` (the target network) inherits the choice."""
     assert precision in ("fp32", "bf16")
+    if precision == "bf16" and getattr(agent.actors[0], "dist_impl", None) == "beta":
+        raise NotImplementedError("set_precision('bf16'): Beta policies (beta_dist=True) are not supported here")
     dev = next(agent.actors[0].parameters()).device
     for owner, key, mods in ([(a, "self", [a]) for a in agent.actors] +
                              [(c, "nets", list(c.nets)) for c in agent.critics]):

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import engine, parallel, rng
+from . import beta, engine, parallel, rng
 from . import learning_utils as lu
 from . import _lib
 from ._lib import check, lib
@@ -210,7 +210,10 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     lu.ensure_adopted(agent, buffer)
     lu.ensure_adopted(target_agent, buffer)
     shard = parallel.shard_of(agent)
-    graphable = (USE_GRAPHS and engine.CAPTURE is None and agent.ensemble_size == 1 and not per
+    is_beta = lu.actor_kind(agent.actors[0]) == "beta"
+    if is_beta and (shard is not None or parallel.member_shard_of(agent) is not None):
+        beta.refuse("critic_update on a critic- or member-sharded agent")
+    graphable = (USE_GRAPHS and engine.CAPTURE is None and agent.ensemble_size == 1 and not per and not is_beta
                  and parallel.member_shard_of(agent) is None
                  and not update_priorities and not dr3_coeff and lu.is_identity(agent.encoder)
                  and random_process is None and torch.cuda.is_available()
@@ -1014,6 +1017,11 @@ def online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_s
               batch_size=batch_size, clip=clip, random_process=random_process, noise_clip=noise_clip,
               augmenter=augmenter, aug_mix=aug_mix, premade_replay_dicts=premade_replay_dicts, per=per,
               discrete=discrete, use_baseline=use_baseline)
+    if lu.actor_kind(agent.actors[0]) == "beta":
+        if use_baseline:
+            beta.refuse("online_actor_update(use_baseline=True)")
+        if parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None:
+            beta.refuse("online_actor_update on a critic- or member-sharded agent")
     dev = log_alphas[0].device
     recordable = (USE_GRAPHS and LAUNCH_MODE == "list" and FUSED_ACTOR and engine.CAPTURE is None
                   and premade_replay_dicts is not None and not discrete and not clip and random_process is None
@@ -1309,8 +1317,18 @@ def _online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_
             A = actor.action_size
             xpi = lu._concat_buffer(ws, f"au.x{i}", s_rep, A)
             logp = ws.get(f"au.logp{i}", (B,))
-            eps = rng.draw_normal((B, A), dev)  # a_dist.rsample() (learning.py:392)
-            if kind == "stochastic":
+            eps = rng.draw_normal((B, A), dev) if kind != "beta" else None  # a_dist.rsample() (learning.py:392)
+            if kind == "beta":
+                # a_dist.rsample() of the Beta head; x is kept for the reparameterised backward
+                xb = beta.sample(agent, aout, B, A, "actor", ws.get(f"au.xb{i}", (B, A)), xpi, S + A, S, logp)
+                use_entropy = 1
+                if random_process is not None:
+                    noise = rng.draw_normal((B, A), dev)
+                    check(lib.ssac_exploration_noise(xpi.data_ptr(), S + A, S, noise.data_ptr(),
+                                                     float(random_process.current_scale),
+                                                     float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
+                    use_entropy = 0
+            elif kind == "stochastic":
                 check(lib.ssac_tanh_normal_fwd(aout.data_ptr(), 2 * A, eps.data_ptr(), B, A,
                                                float(actor.log_std_low), float(actor.log_std_high),
                                                xpi.data_ptr(), S + A, S, logp.data_ptr(), st))
@@ -1369,7 +1387,11 @@ def _online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_
                 parallel.all_reduce_sum(da)
                 dX, n_dx, ld_dx, s_dx, col_dx = da, 1, A, B * A, 0
             d_out = ws.get(f"au.dout{i}", (1, B, a_arena.out_dim))
-            if kind == "stochastic":
+            if kind == "beta":
+                check(lib.ssac_beta_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), 2 * A,
+                                        xb.data_ptr(), B, A, log_alpha.data_ptr(), use_entropy, inv_e, 0,
+                                        d_out.data_ptr(), 2 * A, st))
+            elif kind == "stochastic":
                 check(lib.ssac_tanh_normal_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(),
                                                2 * A, eps.data_ptr(), B, A, float(actor.log_std_low),
                                                float(actor.log_std_high), log_alpha.data_ptr(), use_entropy, inv_e,
@@ -1414,6 +1436,11 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
     prioritised batch whose priorities are refreshed from the advantage afterwards."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
+    if not discrete and lu.actor_kind(agent.actors[0]) == "beta":
+        if filter_:
+            beta.refuse("offline_actor_update with the advantage filter (filter_=True)")
+        if actor_lambda:
+            beta.refuse("offline_actor_update with the action invariance constraint (actor_lambda)")
     E = agent.ensemble_size
     # the BC warm-up (main.py:292-312) trains a pixel encoder THROUGH the BC loss: the actor's input gradient goes
     # back through the conv engine, then clip + encoder_optimizer.step()
@@ -1503,6 +1530,16 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
                 check(lib.ssac_action_invariance_discrete_bwd(
                     out_o.data_ptr(), aout[0, B:].data_ptr(), a_inv.data_ptr(), B, A, float(actor_lambda) * inv_e,
                     d_out[0, B:].data_ptr(), slot[lu.L_ACT_INV:].data_ptr(), slot[lu.L_BC_TOTAL:].data_ptr(), st))
+        elif lu.actor_kind(actor) == "beta":
+            # plain behavioural cloning, loss_i = -mean(log pi(a_data|s)) (learning_utils.py:241-269, filter_=False) with
+            # x = (clamp(a, +-0.99) + 1) / 2; the two loss logs are reduced from log pi on the device
+            xg, lpg = ws.get(f"bc.xb{i}", (B, A)), ws.get(f"bc.lpb{i}", (B,))
+            beta.given_logp(aout, B, A, a, lpg, xg)
+            check(lib.ssac_beta_bwd(0, 0, 0, 0, 0, aout.data_ptr(), 2 * A, xg.data_ptr(), B, A, 0, 0, -inv_e, 1,
+                                    d_out.data_ptr(), 2 * A, st))
+            loss_i = lpg.mean().neg()
+            slot[lu.L_BC0 + i].copy_(loss_i)
+            slot[lu.L_BC_TOTAL].add_(loss_i * inv_e)
         elif det:
             check(lib.ssac_bc_det_logprob_bwd(aout.data_ptr(), A, a.data_ptr(), a.stride(0), mask_ptr, B, A, inv_e,
                                               d_out.data_ptr(), A, slot[lu.L_BC0 + i:].data_ptr(),
@@ -1577,6 +1614,8 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
     ssac_bc_discrete_bwd (log-probability of the data action), ssac_bce_sigmoid_bwd, ssac_markov_smoothness_bwd."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
+    if not discrete and getattr(agent.inverse_model, "dist_impl", None) == "beta":
+        beta.refuse("markov_state_abstraction_update with a Beta inverse model")
     inv, con = agent.inverse_model, agent.contrastive_model
     dev = next(inv.parameters()).device
     ws = lu.agent_ws(agent, dev)
@@ -1712,6 +1751,8 @@ def alpha_update(buffer, agent, optimizers, batch_size, log_alphas, augmenter, a
     logs = {}
     st = engine.stream()
     ms = parallel.member_shard_of(agent)   # member-sharded rank: log_alphas / optimizers are the LOCAL members'
+    if ms is not None and lu.actor_kind(agent.actors[0]) == "beta":
+        beta.refuse("alpha_update on a member-sharded agent")
     for ig in range(agent.ensemble_size if ms is None else ms.ensemble_size):
         i = ig if ms is None else ms.local(ig)
         if i is None:   # a member another rank owns: its host draws, in member order
@@ -1754,6 +1795,9 @@ def alpha_update(buffer, agent, optimizers, batch_size, log_alphas, augmenter, a
                 check(lib.ssac_actor_sample_fused(C.byref(a_arena.desc()), s_rep.data_ptr(), lu._row_stride(s_rep), B,
                                                   eps_ptr, float(actor.log_std_low), float(actor.log_std_high),
                                                   scratch.data_ptr(), A, 0, logp.data_ptr(), 0, 0, 0, rng_ptr, st))
+            elif kind == "beta":
+                # a_dist.log_prob(a_dist.sample()) of the Beta head (learning.py:255)
+                beta.sample(agent, aout, B, A, "alpha", ws.get(f"al.xb{i}", (B, A)), logp=logp)
             elif kind == "stochastic":
                 eps = rng.draw_normal((B, A), dev)  # a_dist.sample() (learning.py:255)
                 scratch = ws.get(f"al.act{i}", (B, A))

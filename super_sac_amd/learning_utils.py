@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import augmentations, engine, nets, rng
+from . import augmentations, beta, engine, nets, rng
 from . import _lib
 from ._lib import check, lib
 
@@ -478,6 +478,8 @@ def actor_kind(actor):
         return "discrete"
     if getattr(actor, "dist_impl", None) == "deterministic":
         return "deterministic"
+    if getattr(actor, "dist_impl", None) == "beta":
+        return "beta"   # (Beta head, beta.py: per-layer path only)
     return "stochastic"
 
 
@@ -553,7 +555,18 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
             x1 = x1_pre
         else:
             x1 = _concat_buffer(ws, f"td.x1.{i}", s1_rep, A)
-        if kind == "stochastic":
+        if kind == "beta":
+            # a' = a_dist_s1.sample() of the Beta head into the [s'|a'] buffer, log pi of that same x (the transform's
+            # cache, learning_utils.py:330-338)
+            beta.sample(agent, aout, B, A, "td", ws.get(f"td.xb{i}", (B, A)), x1, S + A, S, logp)
+            use_entropy = 1
+            if random_process is not None:
+                noise = draw_normal((B, A), dev)
+                check(lib.ssac_exploration_noise(x1.data_ptr(), S + A, S, noise.data_ptr(),
+                                                 float(random_process.current_scale),
+                                                 float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
+                use_entropy = 0
+        elif kind == "stochastic":
             if fuse_sample and IN_KERNEL_NOISE and rng.normal_is_stock():
                 # the noise comes from the agent's Philox stream inside the launch: draw number = host count (eager)
                 # or capture-time count + the device-resident update counter (recorded launch list)
@@ -941,6 +954,8 @@ def member_sharded_softmax_scores(replay_dict, agent, target_agent, member_shard
             check(lib.ssac_ensemble_min_select(q.data_ptr(), c_arena.n_nets, B, c_arena.out_dim, a1.data_ptr(), 1,
                                                row[kg].data_ptr(), st))
         else:
+            if kind == "beta":
+                beta.refuse("softmax backup weights on a member-sharded agent")
             assert kind == "stochastic", "softmax backup weights sample from a stochastic policy"
             A = actor.action_size
             eps = rng.draw_normal((B, A), dev)   # actor_k(s1_rep).sample(): every rank makes every member's draw
@@ -1024,6 +1039,12 @@ def compute_backup_weights(logs, replay_dict, agent, target_agent, weight_type, 
                 _, _, q = engine.mlp_forward(c_arena, s1_rep, lds, 0, B, ws, f"bw.c{k}", save=False)
                 check(lib.ssac_ensemble_min_select(q.data_ptr(), c_arena.n_nets, B, c_arena.out_dim, a1.data_ptr(), 1,
                                                    qmin[k].data_ptr(), st))
+            elif actor_kind(actor) == "beta":
+                A = actor.action_size
+                x1 = _concat_buffer(ws, f"bw.x1.{k}", s1_rep, A)
+                beta.sample(agent, aout, B, A, "backup", ws.get(f"bw.xb{k}", (B, A)), x1, S + A, S)  # actor(s1_rep).sample()
+                _, _, q = engine.mlp_forward(c_arena, x1, S + A, 0, B, ws, f"bw.c{k}", save=False)
+                check(lib.ssac_ensemble_min_select(q.data_ptr(), c_arena.n_nets, B, 1, 0, 0, qmin[k].data_ptr(), st))
             else:
                 A = actor.action_size
                 assert actor_kind(actor) == "stochastic", "softmax backup weights sample from a stochastic policy"

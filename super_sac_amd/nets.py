@@ -75,10 +75,10 @@ class ContinuousStochasticActor(_MLP3):
     def __init__(self, state_size, action_size, log_std_low=-10.0, log_std_high=2.0,
                  hidden_size=256, dist_impl="pyd"):
         super().__init__()
-        assert dist_impl == "pyd", "only the tanh-normal head is on the accelerated path"
+        assert dist_impl in ("pyd", "beta"), f"unknown dist_impl {dist_impl!r}"
         self.log_std_low, self.log_std_high, self.dist_impl = log_std_low, log_std_high, dist_impl
         self.action_size = action_size
-        self._build(state_size, hidden_size, 2 * action_size)
+        self._build(state_size, hidden_size, 2 * action_size)  # (beta: fc3 emits the concentrations' pre-softplus)
 
 
 class ContinuousDeterministicActor(_MLP3):
@@ -101,13 +101,14 @@ class DiscreteActor(_MLP3):
 
 
 class ContinuousInverseModel(_MLP3):
-    """mlps.py:45-76: (s, s') -> tanh-normal over the action that was taken (Markov state abstraction)."""
+    """mlps.py:45-76: (s, s') -> tanh-normal (or Beta, dist_impl="beta") over the action that was taken (Markov state
+    abstraction)."""
     HEAD = "fc3"
 
     def __init__(self, state_size, action_size, log_std_low=-10.0, log_std_high=2.0, hidden_size=256,
                  dist_impl="pyd"):
         super().__init__()
-        assert dist_impl == "pyd", "only the tanh-normal head is on the accelerated path"
+        assert dist_impl in ("pyd", "beta"), f"unknown dist_impl {dist_impl!r}"
         self.log_std_low, self.log_std_high, self.dist_impl = log_std_low, log_std_high, dist_impl
         self.action_size = action_size
         self._build(2 * state_size, hidden_size, 2 * action_size)
