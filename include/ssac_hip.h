@@ -661,6 +661,33 @@ int ssac_drq_shift(const void *src, int src_dtype, const int64_t *idx, int n, in
                    const int64_t *shift, int mode, const float *noise, int n_aug, float *dst,
                    void *stream);
 
+/* ---- Chained augmentations (csrc/ssac_aug.hip): CutoutAug, CutoutColorAug, TranslateAug / LargeTranslateAug, HorizontalFlipAug,
+ * VerticalFlipAug, RotateAug, WindowAug, GammaAug (augmentations.py:83-126, 296-534) and any sequence of them, in ONE pass.
+ * src: uint8 or fp32 images (n x c x h x w) gathered through idx (may be NULL = identity); rows >= n_aug are copied
+ * un-augmented (aug_mix), as in ssac_drq_shift.  ops: device table, row b's chain is ops[b * ops_stride + 0 .. n_ops - 1] in
+ * the order the augmentations are applied (n_ops <= SSAC_AUG_MAX_OPS); the randomisation is drawn on the host.  The chain is
+ * evaluated per output pixel from the last op to the first: geometric ops map the coordinate, a fill ends the walk, the
+ * gammas behind that point are applied to the value in forward order.  dst: fp32 (n x c x h x w), must not alias src.
+ *   op                      i0, i1, i2, i3                                   f0, f1, f2
+ *   SSAC_AUG_NOP            -                                                -
+ *   SSAC_AUG_CUTOUT         rows [i0, i1) x columns [i2, i3) become 0        -
+ *   SSAC_AUG_CUTOUT_COLOR   the same box, on the first 3 * (c / 3) channels  colour of channel ch % 3
+ *   SSAC_AUG_TRANSLATE      out[y, x] = in[y - i0, x - i1]                   colour (ch % 3) where that is outside
+ *   SSAC_AUG_HFLIP / VFLIP  -                                                -
+ *   SSAC_AUG_ROTATE         i0 quarter turns as torch.rot90(k = i0, dims = (2, 3)); 1 and 3 need h == w
+ *   SSAC_AUG_WINDOW         outside rows [i0, i0 + i2) x columns [i1, i1 + i2) becomes 0
+ *   SSAC_AUG_GAMMA          -                                                f0 = gamma: clamp((x / 255) ** f0 * 255, 0, 255)
+ * Gamma: the division is correctly rounded fp32, the power is taken in fp64 and rounded once to fp32. */
+#define SSAC_AUG_MAX_OPS 8
+enum { SSAC_AUG_NOP = 0, SSAC_AUG_CUTOUT = 1, SSAC_AUG_CUTOUT_COLOR = 2, SSAC_AUG_TRANSLATE = 3, SSAC_AUG_HFLIP = 4,
+       SSAC_AUG_VFLIP = 5, SSAC_AUG_ROTATE = 6, SSAC_AUG_WINDOW = 7, SSAC_AUG_GAMMA = 8 };
+typedef struct ssac_aug_op {
+    int32_t op, i0, i1, i2, i3;
+    float f0, f1, f2;
+} ssac_aug_op;
+int ssac_aug_chain(const void *src, int src_dtype, const int64_t *idx, int n, int c, int h, int w,
+                   const ssac_aug_op *ops, int ops_stride, int n_ops, int n_aug, float *dst, void *stream);
+
 /* ==== fused kernels (csrc/ssac_fused.hip): the same arithmetic as the per-layer entry points above,
  * with the activations of a 32-row tile kept in LDS across fc1 -> fc2 -> head.  Supported when
  * ssac_fused_supported() (hidden % 32 == 0, hidden <= 256, out_dim <= 64, LDS carve fits 160 KB);

@@ -6,7 +6,7 @@ Same module / function names as the reference package for the one path it replac
     super_sac_amd.learning.critic_update ...    <- super_sac/learning.py
     super_sac_amd.learning_utils.*              <- super_sac/learning_utils.py
     super_sac_amd.replay.ReplayBuffer           <- super_sac/replay.py (sample path)
-    super_sac_amd.augmentations.*               <- super_sac/augmentations.py (DrQ family)
+    super_sac_amd.augmentations.*               <- super_sac/augmentations.py (DrQ family, cutout ... gamma)
     super_sac_amd.popart.PopArtLayer            <- super_sac/popart.py
     super_sac_amd.nets.*                        <- super_sac/nets/
 
@@ -38,7 +38,8 @@ from .engine import set_precision, sync_shadows  # noqa: E402,F401
 
 
 INSTALLED_AUGMENTATIONS = ("AugmentationSequence", "Drqv2Aug", "DrqAug", "DrqNoNoiseAug", "LargeDrqAug",
-                           "LargeDrqNoNoiseAug", "IdentityAug")
+                           "LargeDrqNoNoiseAug", "IdentityAug", "CutoutAug", "CutoutColorAug", "TranslateAug",
+                           "LargeTranslateAug", "HorizontalFlipAug", "VerticalFlipAug", "RotateAug", "WindowAug", "GammaAug")
 
 
 def install(reference_package):
@@ -52,7 +53,7 @@ def install(reference_package):
 
     The two classes the training scripts construct themselves are rebound as well: ``super_sac.replay.ReplayBuffer``
     (resolved at call time: experiments/gym/train_gym.py:84, dmc/train_dmc_from_pixels.py:62, atari/train_atari.py:41)
-    and the DrQ-family / identity augmentations with their ``AugmentationSequence`` (main.py:138-141 builds the default
+    and the augmentations that have a kernel (INSTALLED_AUGMENTATIONS) with their ``AugmentationSequence`` (main.py:138-141 builds the default
     through the module; a script that did ``from super_sac.augmentations import ...`` BEFORE install() hands over
     reference-built objects, which the update functions adopt in place -- adopt.adopt_augmenter / adopt_buffer)."""
     ref_learning, ref_lu = reference_package.learning, reference_package.learning_utils

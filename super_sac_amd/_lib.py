@@ -179,6 +179,7 @@ SIGNATURES = {
     "ssac_softmax_weights": [_P, _I, _I, _F, _P, _P, _P],
     "ssac_ensemble_min_select": [_P, _I, _I, _I, _P, _L, _P, _P],
     "ssac_drq_shift": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P],
+    "ssac_aug_chain": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
     "ssac_zero": [_P, _L, _P],
     "ssac_im2col": [_P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P],
     "ssac_col2im": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P],

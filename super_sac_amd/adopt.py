@@ -18,10 +18,11 @@ Nothing is copied: weights stay in the torch modules' (re-pointed) parameters, s
 
 The other two objects the training scripts build with the reference's classes are adopted the same way, in place:
 
-  augmenter         a reference ``AugmentationSequence`` (augmentations.py:20-41) whose ``aug_list`` holds DrQ-family /
-                    identity augmentations (:165-293, :489-503, matched by class NAME along the MRO): every element and
-                    the sequence itself change class to this package's; batch size, pad, noise flag and the CURRENT
-                    randomisation (``shift`` / ``w1, h1``) are kept, no host draw is consumed
+  augmenter         a reference ``AugmentationSequence`` (augmentations.py:20-41) whose ``aug_list`` holds DrQ-family,
+                    cutout / translate / flip / rotate / window / gamma or identity augmentations (matched by class NAME
+                    along the MRO, and by the state that class keeps): every element and the sequence itself change
+                    class to this package's; batch size, parameters and the CURRENT randomisation (``shift`` / ``w1, h1``
+                    / ``translation`` ...) are kept, no host draw is consumed
   buffer            a reference ``ReplayBuffer`` (replay.py:140-190: numpy ``ReplayBufferStorage`` + float64 segment
                     trees): the filled rows move into an HBM-resident storage, the trees' arrays become the
                     ``PrioritySampler``'s, counters carry over, and the object becomes a ``replay.ReplayBuffer`` --
@@ -107,7 +108,21 @@ def probe_identity(encoder, obs_dict):
 
 
 # ------------------------------------------------------------------------------------------ augmenters
-_AUG_NAMES = ("Drqv2Aug", "DrqNoNoiseAug", "LargeDrqNoNoiseAug", "LargeDrqAug", "DrqAug", "IdentityAug")
+_AUG_NAMES = ("Drqv2Aug", "DrqNoNoiseAug", "LargeDrqNoNoiseAug", "LargeDrqAug", "DrqAug", "IdentityAug",
+              "CutoutAug", "CutoutColorAug", "LargeTranslateAug", "TranslateAug", "HorizontalFlipAug", "VerticalFlipAug",
+              "RotateAug", "WindowAug", "GammaAug")
+
+# the reference's augmentations this engine refuses, and why
+_AUG_REFUSED = {
+    "GrayscaleAug": "the reference's own implementation (augmentations.py:44-80) raises a broadcasting error unless exactly "
+                    "1 or 3 rows are selected and is not a per-image grayscale when it does run: there is nothing to be on "
+                    "parity with",
+    "RadAug": "it resizes with cv2.resize (augmentations.py:129-162), and no reference output exists to match without it",
+    "ColorJitterAug": "it draws inside forward() and on the device generator and needs per-image reductions "
+                      "(augmentations.py:537-690); not built yet",
+    "NetworkRandomizationAug": "it draws a fresh convolution on the device generator per randomisation and applies it "
+                               "(augmentations.py:774-801); not built yet",
+}
 
 
 def _own_aug_class(obj):
@@ -116,6 +131,14 @@ def _own_aug_class(obj):
         if klass.__name__ in _AUG_NAMES:
             return getattr(A, klass.__name__)
     return None
+
+
+def _refusal(aug):
+    for klass in type(aug).__mro__:
+        if klass.__name__ in _AUG_REFUSED:
+            return f"augmentation {klass.__name__!r} has no HIP path: {_AUG_REFUSED[klass.__name__]}"
+    return (f"augmentation {type(aug).__name__!r} has no HIP path; the update engine runs "
+            f"{', '.join(_AUG_NAMES)} of super_sac/augmentations.py")
 
 
 def adopt_augmenter(augmenter):
@@ -128,23 +151,28 @@ def adopt_augmenter(augmenter):
         raise TypeError(f"{type(augmenter).__name__}: expected an AugmentationSequence (augmentations.py:20-41)")
     swaps = []
     for aug in aug_list:
-        if isinstance(aug, (A._ShiftAug, A.IdentityAug)):
+        if isinstance(aug, (A._ShiftAug, A._ChainAug, A.IdentityAug)):
             swaps.append(None)
             continue
         mine = _own_aug_class(aug)
         if mine is None:
+            raise NotImplementedError(_refusal(aug))
+        # the NAME alone does not make it the reference's class: it has to carry that class's state
+        missing = [n for n in ("batch_size",) + tuple(getattr(mine, "REF_STATE", ())) if not hasattr(aug, n)]
+        if missing:
             raise NotImplementedError(
-                f"augmentation {type(aug).__name__!r} has no HIP path; the update engine runs the DrQ family "
-                f"({', '.join(_AUG_NAMES)}) -- the other augmentations of super_sac/augmentations.py are out of scope")
+                f"augmentation {type(aug).__name__!r} has no HIP path: it is named like the reference's {mine.__name__} "
+                f"but does not carry its state (missing {missing})")
         swaps.append(mine)
     for aug, mine in zip(aug_list, swaps):
         if mine is None:
             continue
-        aug.__dict__.pop("pad_func", None)   # (nn.ReflectionPad2d of the reference's DrqAug: the kernel pads itself)
         aug.__class__ = mine
-        aug._shift_dev = None
-        if not hasattr(aug, "noise"):
-            aug.noise = False
+        if issubclass(mine, A._ShiftAug):
+            aug.__dict__.pop("pad_func", None)   # (nn.ReflectionPad2d of the reference's DrqAug: the kernel pads itself)
+            aug._shift_dev = None
+            if not hasattr(aug, "noise"):
+                aug.noise = False
         aug._adopt_state()
     augmenter.__class__ = A.AugmentationSequence
     return augmenter

@@ -371,6 +371,9 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
         assert augmenter.is_identity(), "image augmentations need image observations"
     else:
         shift_aug = augmenter.single_shift()
+        # cutout / translate / flip / rotate / window / gamma members: one ssac_aug_chain launch per run of them (and one
+        # ssac_drq_shift launch per DrQ-family member of a mixed sequence), the first reading the replay rows through idx
+        passes = augmenter.device_passes() if shift_aug is None else None
         k_aug = int(batch_size * aug_mix)
         o, o1 = {}, {}
         for key in keys:
@@ -383,6 +386,13 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
                     nz = rng.draw_normal((B, c, h, w), dev) if shift_aug.noise else None
                     shift_aug.apply(s_arr, idx, B, c, h, k_aug, out, nz)
                     dst_dict[key] = out
+            elif src.dim() == 4 and passes is not None:
+                c, h, w = src.shape[1:]
+                # (a key outside AugmentationSequence.keys is left alone, augmentations.py:33: gather + convert only)
+                listed = augmenter.keys is None or key in augmenter.keys
+                k_key = k_aug if listed else 0
+                o[key] = passes.run(src, idx, B, c, h, w, k_key, dev)
+                o1[key] = passes.run(src1, idx, B, c, h, w, k_key, dev)
             else:
                 assert augmenter.is_identity(), "unsupported augmentation on the accelerated path"
                 o[key] = st.gather_field(src, idx, B)
@@ -410,6 +420,12 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
                         out = torch.empty(B, c, h, w, device=dev)
                         shift_aug.apply(src, idx, B, c, h, n_aug, out, None)
                         dst_dict[key] = out
+                elif src.dim() == 4 and passes is not None:
+                    c, h, w = src.shape[1:]
+                    listed = augmenter.keys is None or key in augmenter.keys
+                    k_key = k_aug if listed else 0
+                    for dst_dict, n_aug in ((ao, B if listed else 0), (oo, 0)):
+                        dst_dict[key] = o[key] if n_aug == k_key else passes.run(src, idx, B, c, h, w, n_aug, dev)
                 else:
                     ao[key] = oo[key] = o[key]
             inv_obs = ((ao, None), (oo, None))

@@ -2,6 +2,9 @@
 so a run that swaps in this engine consumes them identically:
 
   replay indices, DrQ shifts      torch CPU default generator   (replay.py:122, augmentations.py:227)
+  cutout / translate / rotate /   torch CPU default generator   (augmentations.py:99, 311, 386, 477, 526)
+  window parameters
+  flip rows, gamma exponents      numpy's global generator      (augmentations.py:412, 441)
   REDQ target subset, logged net  Python ``random``             (agent.py:29, learning.py:135)
   action noise eps                generator of the compute device (distributions: Normal.sample)
   Beta policy draws x             the agent's engine Philox stream, inside ssac_beta_fwd (beta_dist=True)
@@ -15,6 +18,7 @@ Parity tests replace these functions to replay the draws recorded in tests/golde
 """
 import random
 
+import numpy as np
 import torch
 
 
@@ -84,3 +88,49 @@ def draw_drq_offsets(batch_size, pad):
     w1 = torch.randint(0, pad * 2, (batch_size,))
     h1 = torch.randint(0, pad * 2, (batch_size,))
     return w1, h1
+
+
+# ---- chained augmentations (augmentations.py:83-126, 296-534): the reference's generators, in the reference's order
+def draw_cutout_box(batch_size, box_min, box_max):
+    """CutoutAug (augmentations.py:99-100, 118-119): w1 then h1 on torch's CPU generator"""
+    w1 = torch.randint(box_min, box_max, (batch_size,))
+    h1 = torch.randint(box_min, box_max, (batch_size,))
+    return w1, h1
+
+
+def draw_cutout_color(batch_size, box_min, box_max):
+    """CutoutColorAug (augmentations.py:385-393): w1, h1, then the box colour"""
+    w1 = torch.randint(box_min, box_max, (batch_size,))
+    h1 = torch.randint(box_min, box_max, (batch_size,))
+    rand_box = torch.randint(0, 255, size=(batch_size, 3, 1, 1), dtype=torch.float32)
+    return w1, h1, rand_box
+
+
+def draw_translation(batch_size, translate_max):
+    """TranslateAug (augmentations.py:309-316): the (dy, dx) translation, then the border colour"""
+    translation = torch.randint(2 * translate_max, (batch_size, 2), dtype=torch.int32) - translate_max
+    random_color = torch.randint(255, size=(batch_size, 3, 1, 1)).float()
+    return translation, random_color
+
+
+def draw_flip_rows(batch_size, p):
+    """_FlipAug (augmentations.py:440-443): numpy's global generator"""
+    return np.random.choice([True, False], batch_size, p=[p, 1 - p])
+
+
+def draw_rotation(batch_size):
+    """RotateAug (augmentations.py:476-480): torch.randint(4) * B + arange(B) -- see augmentations.RotateAug on what the
+    reference then does with these values"""
+    return torch.randint(4, size=(batch_size,)) * batch_size + torch.from_numpy(np.arange(batch_size))
+
+
+def draw_window(batch_size, crop_max):
+    """WindowAug (augmentations.py:525-527): w1 then h1"""
+    w1 = torch.randint(0, crop_max, (batch_size,))
+    h1 = torch.randint(0, crop_max, (batch_size,))
+    return w1, h1
+
+
+def draw_gamma(batch_size, mean, std):
+    """GammaAug (augmentations.py:411-415): numpy's global generator, cast to float32, shaped (B, 1, 1, 1)"""
+    return torch.from_numpy(np.random.normal(mean, std, size=(batch_size,))).float().view(-1, 1, 1, 1)
