@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 7
+#define SSAC_ABI_VERSION 8
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -1069,7 +1069,7 @@ int ssac_act_add_list(ssac_act *a, ssac_launch_list *list);   /* returns the lis
 int ssac_act_run(ssac_act *a, int which, const void *obs_host, int obs_bytes, float *out_host, int out_floats, void *stream);
 long long ssac_act_calls(const ssac_act *a);
 void ssac_act_destroy(ssac_act *a);
-/* SUNRISE's UCB rule (agent.py:262-300) on stacked candidates: q_members[c] (HOST array of n_members <= 8 device pointers) =
+/* SUNRISE's UCB rule (agent.py:262-300) on stacked candidates: q_members[c] (HOST array of n_members <= 32 device pointers) =
  * member c's critics on row (a n_rows + b) of X, (n_nets x n_cand n_rows); a candidate's value per member = min over its nets
  * (agent.Critic.forward), score = mean over the members + bonus * unbiased std, best = first arg-max over the candidates;
  * act (n_rows x act_dim) = columns [col0, col0 + act_dim) of X's row (best n_rows + b), clamped to [-1, 1]. */
@@ -1092,6 +1092,17 @@ int ssac_act_take_clamp(const float *src, int64_t ld, int col0, int n_rows, int 
  * the action index as a float. */
 int ssac_act_discrete(const float *const *outs, int n_actors, int64_t ld_out, int n_rows, int n_actions, int sample,
                       const ssac_rng *rng, float *act, void *stream);
+/* the pointer arrays of ssac_ucb_select / ssac_act_mean_tanh / ssac_act_discrete hold at most SSAC_ACT_MAX_MEMBERS entries */
+#define SSAC_ACT_MAX_MEMBERS 32
+/* SUNRISE's UCB rule for discrete agents (agent.py:259-304, the `if self.discrete:` branch) in one launch behind the packed
+ * forwards.  logits (n_members x n_rows x n_actions): every actor's head output; q (n_members n_nets x n_rows x n_actions):
+ * every member's critics on the state representation, member c's nets at [c n_nets, (c + 1) n_nets).  Per row b: candidate
+ * a_e = Categorical(logits[e][b]).sample() by inversion, ssac_act_discrete's arithmetic with the uniform of draw rng->offset +
+ * e member_stride (+ *rng->counter); value of a_e for member c = min over its nets of q[.][b][a_e]; score = mean over the
+ * members + bonus * unbiased std; act[b] = a_e of the first arg-max over e, as a float.  2 <= n_members <= 32, n_actions <= 64.
+ * One wavefront per row, every reduction in index order: the same bits on every run. */
+int ssac_act_ucb_discrete(const float *logits, const float *q, int n_members, int n_nets, int n_rows, int n_actions,
+                          float bonus, const ssac_rng *rng, long long member_stride, float *act, void *stream);
 
 /* zero a float buffer (log accumulators) */
 int ssac_zero(float *p, int64_t n, void *stream);

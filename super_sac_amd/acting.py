@@ -8,11 +8,19 @@ the publish step -- into a launch list of an ``ssac_act`` plan; every later call
 written straight into device-visible memory, the list is re-issued, the action arrives in pinned host memory.  No torch op,
 no hipMemcpy, no stream synchronisation.  Measured (bench.py ``secondary.acting``): see profiles/r6_acting.md.
 
-What stays on the general path (agent.py's eager code, unchanged): pixel encoders, injected noise (a hook on
-``rng.draw_normal`` -- the parity tests), discrete UCB, networks outside the fused kernels' shapes (hidden > 256),
-``from_cpu=False`` callers, Beta actors (beta_dist=True).  Host RNG contract: the Python ``random`` draws of the reference (``random.choice`` of the
+Discrete agents under SUNRISE's UCB rule (agent.py:259-304, the ``if self.discrete:`` branch) record the packed actors' and the
+packed critics' forwards on the state representation and ONE reduction launch (ssac_act_ucb_discrete: a categorical draw per
+member, the gather, mean + bonus * std, arg-max); their plan is keyed ("sample", n, bonus).  A pack above SSAC_MAX_NETS
+networks is forwarded by several packed launches inside the same list; the reductions take up to 32 members.
+
+What stays on the general path (agent.py's eager code, unchanged): rolling encoders, float-frame observations, injected noise
+(a hook on ``rng.draw_normal`` -- the parity tests), ensembles above 32 members, UCB networks outside the fused kernels' shapes
+(hidden > 256), ``from_cpu=False`` callers, Beta actors (beta_dist=True), and every (agent, rule, num_envs) whose recording
+failed once (the call that met the failure included: it is served by the general path, the key is not tried again).  Host RNG contract: the Python ``random`` draws of the reference (``random.choice`` of the
 acting actor / of the logged distribution) are consumed exactly as before."""
 import ctypes as C
+import random
+import warnings
 import weakref
 
 import numpy as np
@@ -24,7 +32,10 @@ from ._lib import check, lib
 
 ENABLED = True
 _PLANS = weakref.WeakKeyDictionary()   # agent -> {(rule, num_envs, bonus): _Plan}
+_FAILED = weakref.WeakKeyDictionary()  # agent -> {plan key}: a recording failed, the general path serves the key from then on
 _SERIAL = [0]
+MAX_MEMBERS = 32                       # SSAC_ACT_MAX_MEMBERS: what the rules' reduction kernels take
+MAX_NETS = 64                          # SSAC_MAX_NETS: the networks of ONE packed forward launch
 _STREAM_SALT = 0x41C7A11D5EEDB00C      # the acting noise stream: the agent's engine seed under another key
 
 
@@ -116,31 +127,55 @@ def _eligible(agent, obs, num_envs, sample, rolling):
     elif rolling or _pixel_obs(agent, obs, num_envs) is None:
         return False          # (a rolling encoder keeps state between calls: the general path)
     E = len(agent.actors)
-    if E > 8 or agent.act_space_size > 64:
+    if E > MAX_MEMBERS or agent.act_space_size > 64:
         return False
     kind = lu.actor_kind(agent.actors[0])
     if kind == "beta":
         return False          # (the recorded rules sample the tanh-normal head: Beta actors act on the general path)
     if sample and kind == "stochastic" and not rng.normal_is_stock():
         return False          # injected noise: the general path draws it through the hook
-    if sample and agent.ucb_bonus > 0 and (agent.discrete or kind != "stochastic" or E < 2):
+    if sample and agent.ucb_bonus > 0 and (kind not in ("stochastic", "discrete") or E < 2 or len(agent.critics) != E):
         return False
     return True
 
 
-def _arena_ok(agent, dev, with_critics):
+def _arena_ok(agent, dev, with_critics, sample):
     """every network the rule touches has a launchable forward: the fused MLP kernel, or -- networks outside its shapes, e.g.
     DrQv2's hidden-1024 actor -- the per-layer GEMM family (three launches); the UCB rule's sampling kernels are fused-only"""
     arenas = [engine.bind_arena(a, "self", [a], dev) for a in agent.actors]
+    if len(arenas) > 1 and (with_critics or not sample) and not _packable(arenas):
+        return False          # (the rules that pack the actors: forward, the UCB rules; a plain sample is one actor's launch)
     if with_critics:
-        return all(a.fused for a in arenas) and all(c.arena(dev).fused for c in agent.critics)
+        # the UCB rules: two packs (the members' shapes and, for the tanh-normal head, the log-std bounds must agree), a
+        # member's critics inside one packed launch, the reduction's member and action limits
+        c_arenas = [c.arena(dev) for c in agent.critics]
+        a0 = agent.actors[0]
+        if not agent.discrete and any((float(a_.log_std_low), float(a_.log_std_high)) !=
+                                      (float(a0.log_std_low), float(a0.log_std_high)) for a_ in agent.actors):
+            return False
+        return (all(a.fused for a in arenas) and all(c.fused for c in c_arenas) and _packable(c_arenas)
+                and len(c_arenas) == len(arenas) and 2 <= len(arenas) <= MAX_MEMBERS
+                and all(c.n_nets == c_arenas[0].n_nets for c in c_arenas) and 1 <= c_arenas[0].n_nets <= MAX_NETS
+                and agent.act_space_size <= 64)
     return all(a.fused for a in arenas) or lu.actor_kind(agent.actors[0]) != "stochastic"
+
+
+def _packable(arenas):
+    a0 = arenas[0]
+    return all((a.in_dim, a.hidden, a.out_dim, a.stride) == (a0.in_dim, a0.hidden, a0.out_dim, a0.stride) for a in arenas)
 
 
 def _fwd_desc(plan, desc, n_nets, fused, hidden, out_dim, x_ptr, ldx, n_rows, y):
     """y (n_nets x n_rows x out) = MLP(x) for every net of `desc` (shared input rows): one fused launch, or three per-layer
-    launches through plan-owned activations (mlps.py:123-129)"""
+    launches through plan-owned activations (mlps.py:123-129).  More than SSAC_MAX_NETS nets: one such launch (group) per
+    SSAC_MAX_NETS nets, each on its slice of the arena and of y"""
     st = engine.stream()
+    if n_nets > MAX_NETS:
+        for k0 in range(0, n_nets, MAX_NETS):
+            k = min(MAX_NETS, n_nets - k0)
+            part = _lib.MlpDesc(desc.params + 4 * k0 * desc.net_stride, desc.net_stride, k, desc.in_dim, desc.hidden, desc.out_dim)
+            _fwd_desc(plan, part, k, fused, hidden, out_dim, x_ptr, ldx, n_rows, y[k0:k0 + k])
+        return
     if fused:
         check(lib.ssac_mlp3_fwd_fused(C.byref(desc), 0, n_nets, x_ptr, ldx, 0, n_rows, 0, 0, y.data_ptr(), st))
         return
@@ -190,6 +225,17 @@ def _pack_launch(packs):
 
 
 def _record(plan, agent, which):
+    """_record_launches, or False when it failed: whatever a launch refused (a shape outside its limits, a pack the arena
+    checks did not foresee) must not reach the environment loop -- the caller drops the plan and the general path acts"""
+    try:
+        _record_launches(plan, agent, which)
+    except Exception as exc:   # noqa: BLE001  (a refused launch raises RuntimeError, a broken expectation AssertionError)
+        plan.error = f"{type(exc).__name__}: {exc}"
+        return False
+    return True
+
+
+def _record_launches(plan, agent, which):
     """record the launches of plan.rule for acting actor `which` (None: the rule involves every actor)"""
     dev, n, S, A = plan.dev, plan.n, plan.S, plan.A
     st = engine.stream()
@@ -201,6 +247,7 @@ def _record(plan, agent, which):
         plan.res = plan.buf(max(plan.out_floats, 1))
         plan.logp = plan.buf(max(n * E, 1))
     check(lib.ssac_record_begin())
+    done = False
     try:
         x_in = plan.obs_dev      # what the actors read: the observation itself, or the encoder's output
         if plan.pixel_shape is not None:
@@ -244,10 +291,30 @@ def _record(plan, agent, which):
                        for a_ in agent.actors)
             check(lib.ssac_act_candidates(packed_out.data_ptr(), E, n, A, x_in, S, S, float(a0.log_std_low),
                                           float(a0.log_std_high), C.byref(r), 1 << 40, x.data_ptr(), S + A, st))
-            check(lib.ssac_mlp3_fwd_fused(C.byref(pc.desc), 0, pc.n_nets, x.data_ptr(), S + A, 0, E * n, 0, 0, q.data_ptr(), st))
+            # (a pack above SSAC_MAX_NETS critics -- 8 members x 10 -- goes out as several packed launches)
+            _fwd_desc(plan, pc.desc, pc.n_nets, True, pc.hidden, 1, x.data_ptr(), S + A, E * n, q)
             qs = [q[c * N:(c + 1) * N] for c in range(len(c_arenas))]
             check(lib.ssac_ucb_select(_ptr_array(qs), len(qs), N, E, n, float(agent.ucb_bonus), x.data_ptr(), S + A, S, A,
                                       plan.res.data_ptr(), st))
+        elif plan.rule == "ducb":
+            # agent.py:259-304, the discrete branch: a categorical candidate per actor, every member's critics on the state
+            # representation (all A values of a row in one pass: no stacked candidates), the value of every candidate for
+            # every member, mean + bonus * std over the members, arg-max over the candidates.  Five launches whatever the
+            # ensemble size (below SSAC_MAX_NETS critics): the two packs, ONE forward of all actors, ONE of all critics, the
+            # rule's kernel (member e draws at offset e << 40 of the plan's stream), the publish step
+            c_arenas = [c.arena(dev) for c in agent.critics]
+            pa, pc = _Pack(plan, arenas), _Pack(plan, c_arenas)
+            assert pa.out_dim == A and pc.out_dim == A and pa.fused and pc.fused and len(c_arenas) == E
+            packed_out = plan.buf(E, n, A)
+            plan.outs = [packed_out[e] for e in range(E)]
+            N = c_arenas[0].n_nets
+            q = plan.buf(pc.n_nets, n, A)
+            _pack_launch([pa, pc])
+            _fwd_desc(plan, pa.desc, E, True, pa.hidden, A, x_in, S, n, packed_out)
+            _fwd_desc(plan, pc.desc, pc.n_nets, True, pc.hidden, A, x_in, S, n, q)
+            r = plan.rng_for(agent, 0)
+            check(lib.ssac_act_ucb_discrete(packed_out.data_ptr(), q.data_ptr(), E, N, n, A, float(agent.ucb_bonus), C.byref(r),
+                                            1 << 40, plan.res.data_ptr(), st))
         else:   # "sample": one actor's draw (agent.py:301-309)
             actor, ar, out = agent.actors[which], arenas[which], plan.outs[which]
             if plan.discrete:
@@ -264,12 +331,17 @@ def _record(plan, agent, which):
                 _fwd(plan, ar, x_in, S, n, out)
                 check(lib.ssac_act_mean_tanh(_ptr_array([out]), 1, ar.out_dim, n, A, plan.res.data_ptr(), st))
         check(lib.ssac_act_publish(plan.handle, plan.res.data_ptr(), plan.out_floats, st))
+        done = True
     finally:
         lst = lib.ssac_record_end()
+        if not done and lst:
+            lib.ssac_launch_list_free(lst)   # (the partial list of a recording that failed)
     # (the recording pass issued the launches too -- on whatever the observation buffer held -- and advanced the device-side
     #  call counter: ssac_act_add_list drains the device and re-reads the count)
     idx = lib.ssac_act_add_list(plan.handle, lst)
     if idx < 0:
+        if lst:
+            lib.ssac_launch_list_free(lst)   # (not taken over by the plan)
         raise RuntimeError("libssac_hip: " + lib.ssac_last_error().decode())
     plan.lists[which] = idx
 
@@ -280,16 +352,18 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
         return None
     dev = next(agent.actors[0].parameters()).device
     ucb = bool(sample and agent.ucb_bonus > 0)
-    rule = "ucb" if ucb else ("sample" if sample else "forward")
-    plans = _PLANS.setdefault(agent, {})
-    pkey = (rule, num_envs, float(agent.ucb_bonus) if ucb else 0.0)
-    plan = plans.get(pkey)
+    rule = ("ducb" if agent.discrete else "ucb") if ucb else ("sample" if sample else "forward")
+    # (the discrete UCB rule is keyed as the sample rule it replaces, told apart by its bonus)
+    pkey = ("sample" if rule == "ducb" else rule, num_envs, float(agent.ucb_bonus) if ucb else 0.0)
+    failed = _FAILED.get(agent)
+    if failed and pkey in failed:
+        return None
+    plans = _PLANS.get(agent)
+    plan = None if plans is None else plans.get(pkey)
     sig = _signature(agent, ucb)
     if plan is None or plan.sig != sig:
-        if not _arena_ok(agent, dev, ucb):
+        if not _arena_ok(agent, dev, ucb, sample):
             return None
-        if len(plans) > 12:
-            plans.clear()
         pix = None if lu.is_identity(agent.encoder) else _pixel_obs(agent, obs, num_envs)
         eng = None
         if pix is not None:
@@ -297,18 +371,33 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
             eng = conv_encoder.conv_engine(agent.encoder, dev)   # (the module's own engine: its parameters live in its arena)
             if eng is None:
                 return None
+        plans = _PLANS.setdefault(agent, {})
+        if len(plans) > 12:
+            plans.clear()
         plan = plans[pkey] = _Plan(agent, rule, num_envs, dev, pixel_shape=None if pix is None else pix[1])
         plan.conv_engine = eng
         plan.sig = _signature(agent, ucb)   # (binding the arenas may have re-pointed the parameters)
     # the reference's host draws, in its order: random.choice(act_dists) under UCB (for the logged distribution),
     # random.choice(self.actors) otherwise (agent.py:262, 301)
     which = None
-    if rule == "ucb":
+    # (a recording may fail and hand the call to the general path, which makes the host draw itself: the generator's state
+    #  is kept -- a ~2 us copy -- only while the plan still has a list to record, i.e. for the first few calls of a plan)
+    host_state = random.getstate() if len(plan.lists) < (len(agent.actors) if rule == "sample" else 1) else None
+    if ucb:
         which_dist = rng.choice(range(len(agent.actors)))
     elif rule == "sample":
         which = which_dist = rng.choice(range(len(agent.actors)))
-    if which not in plan.lists:
-        _record(plan, agent, which)
+    if which not in plan.lists and not _record(plan, agent, which):
+        # the recording failed: no half-built plan stays behind, the key is not tried again, and the general path serves
+        # this call -- it makes the reference's host draw itself, so the one made above is handed back
+        _FAILED.setdefault(agent, {})[pkey] = plan.error
+        warnings.warn(f"super_sac_amd.acting: recording the {rule} rule for {num_envs} environment(s) failed ({plan.error}); "
+                      "these calls take the general path from now on", RuntimeWarning, stacklevel=3)
+        plans.pop(pkey, None)
+        if not plans:
+            _PLANS.pop(agent, None)
+        random.setstate(host_state)
+        return None
     v = np.ascontiguousarray(obs[plan.key], dtype=np.float32 if plan.pixel_shape is None else np.uint8)
     rc = lib.ssac_act_run(plan.handle, plan.lists[which], v.ctypes.data, v.nbytes, plan.result.ctypes.data, plan.out_floats,
                           engine.stream())

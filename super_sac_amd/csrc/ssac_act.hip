@@ -26,9 +26,12 @@
 
 namespace {
 
+// ensembles of up to ACT_MAX_E members take the kernels instantiated for 8 pointers (the launches of every ensemble the
+// path served before it took larger ones: same code, same bits); up to ACT_MAX_E_WIDE members the same kernels with 32
 constexpr int ACT_MAX_E = 8;
+constexpr int ACT_MAX_E_WIDE = 32;
 
-struct PtrList { const float *p[ACT_MAX_E]; };
+template <int MAXE> struct PtrList { const float *p[MAXE]; };
 
 // ---- publish: result -> pinned host memory, then the sequence word (what the host spins on), counter += 1
 __global__ __launch_bounds__(256) void act_publish_kernel(const float *__restrict__ src, int n, float *dst,
@@ -48,7 +51,8 @@ __global__ __launch_bounds__(256) void act_publish_kernel(const float *__restric
 // (n_nets x n_cand n_rows); value of candidate a for member c = min over its nets (agent.Critic.forward, return_min);
 // score = mean_c + bonus * std_c (unbiased, torch.std); best = first arg-max over a (torch.argmax); the action = columns
 // [col0, col0 + A) of X's row (best n_rows + b), clamped to [-1, 1] (_process_act).
-__global__ void ucb_select_kernel(PtrList q, int n_members, int n_nets, int n_cand, int n_rows, float bonus,
+template <int MAXE>
+__global__ void ucb_select_kernel(PtrList<MAXE> q, int n_members, int n_nets, int n_cand, int n_rows, float bonus,
                                   const float *__restrict__ X, int64_t ldx, int col0, int A, float *__restrict__ act) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_rows) return;
@@ -56,23 +60,35 @@ __global__ void ucb_select_kernel(PtrList q, int n_members, int n_nets, int n_ca
     int best = 0;
     float best_v = 0.0f;
     for (int a = 0; a < n_cand; ++a) {
-        float v[ACT_MAX_E];   // (constant trip counts + guards: the array stays in registers)
-        float sum = 0.0f;
+        float sum = 0.0f, ss = 0.0f, mean;
+        if constexpr (MAXE <= 8) {
+            float v[MAXE];   // (constant trip counts + guards: the array stays in registers)
 #pragma unroll
-        for (int c = 0; c < ACT_MAX_E; ++c) {
-            v[c] = 0.0f;
-            if (c < n_members) {
+            for (int c = 0; c < MAXE; ++c) {
+                v[c] = 0.0f;
+                if (c < n_members) {
+                    float m = q.p[c][(int64_t)a * n_rows + b];
+                    for (int j = 1; j < n_nets; ++j) m = fminf(m, q.p[c][j * per_net + (int64_t)a * n_rows + b]);
+                    v[c] = m;
+                    sum += m;
+                }
+            }
+            mean = sum / (float)n_members;
+#pragma unroll
+            for (int c = 0; c < MAXE; ++c)
+                if (c < n_members) ss += (v[c] - mean) * (v[c] - mean);
+        } else {
+            // (the wide form reads the members' values twice instead of keeping 32 of them, and takes member c's pointer
+            //  from the kernel arguments by index: the same operations in the same order, no register array, no scratch)
+            auto value = [&](int c) {
                 float m = q.p[c][(int64_t)a * n_rows + b];
                 for (int j = 1; j < n_nets; ++j) m = fminf(m, q.p[c][j * per_net + (int64_t)a * n_rows + b]);
-                v[c] = m;
-                sum += m;
-            }
+                return m;
+            };
+            for (int c = 0; c < n_members; ++c) sum += value(c);
+            mean = sum / (float)n_members;
+            for (int c = 0; c < n_members; ++c) { const float d = value(c) - mean; ss += d * d; }
         }
-        const float mean = sum / (float)n_members;
-        float ss = 0.0f;
-#pragma unroll
-        for (int c = 0; c < ACT_MAX_E; ++c)
-            if (c < n_members) ss += (v[c] - mean) * (v[c] - mean);
         const float score = mean + bonus * sqrtf(ss / (float)(n_members - 1));
         if (a == 0 || score > best_v) { best = a; best_v = score; }
     }
@@ -104,7 +120,8 @@ __global__ void ucb_candidates_kernel(const float *__restrict__ outs, int n_acto
 
 // ---- greedy continuous action (agent.py:204-246): mean over the actors of dist.mean = tanh(mu) (SquashedNormal.mean /
 // the deterministic actor's tanh(out)), clamped
-__global__ void mean_tanh_kernel(PtrList outs, int n_actors, int64_t ld_out, int n_rows, int A, float *__restrict__ act) {
+template <int MAXE>
+__global__ void mean_tanh_kernel(PtrList<MAXE> outs, int n_actors, int64_t ld_out, int n_rows, int A, float *__restrict__ act) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows * A) return;
     const int b = i / A, k = i - b * A;
@@ -125,15 +142,16 @@ __global__ void take_clamp_kernel(const float *__restrict__ src, int64_t ld, int
 // ---- discrete actors.  greedy: arg-max of the mean over the actors of softmax(logits) (agent.py:218-226); sample:
 // Categorical(logits).sample() of ONE actor (agent.py:301-309) by inversion of the cumulative distribution with one
 // uniform per row from the engine's Philox stream (element (row, 0) of the draw's first word).  The index leaves as a float.
-__global__ void discrete_act_kernel(PtrList outs, int n_actors, int64_t ld_out, int n_rows, int A, int sample, RngArgs rng,
+template <int MAXE>
+__global__ void discrete_act_kernel(PtrList<MAXE> outs, int n_actors, int64_t ld_out, int n_rows, int A, int sample, RngArgs rng,
                                     float *__restrict__ act) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_rows) return;
     // per-actor softmax statistics in registers (constant trip counts + guards), the mean probability of an action recomputed
     // where it is needed: no per-thread array indexed at run time, no scratch memory
-    float mx[ACT_MAX_E], rz[ACT_MAX_E];
+    float mx[MAXE], rz[MAXE];
 #pragma unroll
-    for (int e = 0; e < ACT_MAX_E; ++e) {
+    for (int e = 0; e < MAXE; ++e) {
         mx[e] = 0.0f; rz[e] = 0.0f;
         if (e < n_actors) {
             const float *o = outs.p[e] + b * ld_out;
@@ -147,7 +165,7 @@ __global__ void discrete_act_kernel(PtrList outs, int n_actors, int64_t ld_out, 
     auto prob = [&](int k) {
         float pk = 0.0f;
 #pragma unroll
-        for (int e = 0; e < ACT_MAX_E; ++e)
+        for (int e = 0; e < MAXE; ++e)
             if (e < n_actors) pk += expf(outs.p[e][b * ld_out + k] - mx[e]) * rz[e];
         return pk;
     };
@@ -174,6 +192,69 @@ __global__ void discrete_act_kernel(PtrList outs, int n_actors, int64_t ld_out, 
         }
     }
     act[b] = (float)pick;
+}
+
+// ---- SUNRISE's UCB rule for DISCRETE agents (agent.py:259-304, the `if self.discrete:` branch) behind the packed forwards.
+// logits (n_members x n_rows x A): every actor's head output; q (n_members n_nets x n_rows x A): every member's critics on
+// the state representation.  One wavefront per environment b, lane e = member e's candidate:
+//   a_e   = Categorical(logits[e, b]).sample() by inversion of the cumulative distribution -- discrete_act_kernel's
+//           arithmetic, operation for operation -- with the uniform of (row b, draw rng.offset + e * member_stride
+//           (+ *rng.counter)): member e draws what ssac_act_discrete with that offset would draw;
+//   v_c   = min over member c's nets of q[., b, a_e] (agent.Critic.forward, return_min), c = 0, 1, ... in index order;
+//   score = mean_c v_c + bonus * std_c v_c (unbiased, torch.std).
+// The arg-max over the candidates is a scan of lanes 0, 1, ... in order through the wave's cross-lane reads, the same scan
+// in every lane (first maximum: torch.argmax): no LDS, no atomics, one plain store of the index (as a float) by lane 0.
+__global__ __launch_bounds__(64) void ucb_discrete_kernel(const float *__restrict__ logits, int n_members, int n_nets,
+                                                         int n_rows, int A, const float *__restrict__ q, float bonus,
+                                                         RngArgs rng, long long member_stride, float *__restrict__ act) {
+    const int b = blockIdx.x, e = threadIdx.x;
+    int pick = 0;
+    float score = 0.0f;
+    if (e < n_members) {
+        const float *o = logits + ((int64_t)e * n_rows + b) * A;
+        float m = o[0];
+        for (int k = 1; k < A; ++k) m = fmaxf(m, o[k]);
+        float z = 0.0f;
+        for (int k = 0; k < A; ++k) z += expf(o[k] - m);
+        const float rz = 1.0f / z;
+        uint32_t c[4] = {(uint32_t)b, 0u, 0u, 0u};
+        const int64_t draw = rng_draw(rng) + (int64_t)e * member_stride;
+        c[2] = (uint32_t)draw; c[3] = (uint32_t)((uint64_t)draw >> 32);
+        philox4x32_10(c, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32));
+        float tot = 0.0f;
+        for (int k = 0; k < A; ++k) tot += expf(o[k] - m) * rz;
+        const float u = (float)c[0] * 2.3283064365386963e-10f * tot;   // [0, tot)
+        float cum = 0.0f;
+        pick = A - 1;
+        for (int k = 0; k < A; ++k) {
+            cum += expf(o[k] - m) * rz;
+            if (u < cum) { pick = k; break; }
+        }
+        const int64_t per_net = (int64_t)n_rows * A;
+        const float *qa = q + (int64_t)b * A + pick;
+        auto value = [&](int c_) {
+            float v = qa[(int64_t)c_ * n_nets * per_net];
+            for (int j = 1; j < n_nets; ++j) v = fminf(v, qa[((int64_t)c_ * n_nets + j) * per_net]);
+            return v;
+        };
+        float sum = 0.0f;
+        for (int c_ = 0; c_ < n_members; ++c_) sum += value(c_);
+        const float mean = sum / (float)n_members;
+        float ss = 0.0f;
+        for (int c_ = 0; c_ < n_members; ++c_) {
+            const float d = value(c_) - mean;
+            ss += d * d;
+        }
+        score = mean + bonus * sqrtf(ss / (float)(n_members - 1));
+    }
+    int best = 0;
+    float best_v = 0.0f;
+    for (int a = 0; a < n_members; ++a) {   // (n_members is uniform: every lane of the wave takes part in every read)
+        const float s = __shfl(score, a);
+        const int p = __shfl(pick, a);
+        if (a == 0 || s > best_v) { best = p; best_v = s; }
+    }
+    if (e == 0) act[b] = (float)best;
 }
 
 }  // namespace
@@ -288,20 +369,28 @@ extern "C" void ssac_act_destroy(ssac_act *a) {
 }
 
 // ---- the acting rules' reductions (launchable on their own, recordable)
-static int fill_ptrs(PtrList &pl, const float *const *ptrs, int n, const char *who) {
-    if (!ptrs || n <= 0 || n > ACT_MAX_E) return ssac_fail(who);
-    for (int i = 0; i < ACT_MAX_E; ++i) pl.p[i] = ptrs[i < n ? i : 0];
+template <int MAXE>
+static int fill_ptrs(PtrList<MAXE> &pl, const float *const *ptrs, int n, const char *who) {
+    if (!ptrs || n <= 0 || n > MAXE) return ssac_fail(who);
+    for (int i = 0; i < MAXE; ++i) pl.p[i] = ptrs[i < n ? i : 0];
     return 0;
 }
 
 extern "C" int ssac_ucb_select(const float *const *q_members, int n_members, int n_nets, int n_cand, int n_rows, float bonus,
                                const float *X, int64_t ldx, int col0, int act_dim, float *act, void *stream) {
-    PtrList pl;
-    if (fill_ptrs(pl, q_members, n_members, "ssac_ucb_select: 1..8 members")) return 1;
     if (n_members < 2 || n_nets <= 0 || n_cand <= 0 || n_rows <= 0 || !X || !act || act_dim <= 0)
         return ssac_fail("ssac_ucb_select: bad arguments (the unbiased std needs >= 2 members)");
-    SSAC_LAUNCH(ucb_select_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_members, n_nets, n_cand, n_rows, bonus, X,
-                ldx, col0, act_dim, act);
+    if (n_members <= ACT_MAX_E) {
+        PtrList<ACT_MAX_E> pl;
+        if (fill_ptrs(pl, q_members, n_members, "ssac_ucb_select: 2..32 members")) return 1;
+        SSAC_LAUNCH(ucb_select_kernel<ACT_MAX_E>, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_members, n_nets, n_cand,
+                    n_rows, bonus, X, ldx, col0, act_dim, act);
+    } else {
+        PtrList<ACT_MAX_E_WIDE> pl;
+        if (fill_ptrs(pl, q_members, n_members, "ssac_ucb_select: 2..32 members")) return 1;
+        SSAC_LAUNCH(ucb_select_kernel<ACT_MAX_E_WIDE>, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_members, n_nets, n_cand,
+                    n_rows, bonus, X, ldx, col0, act_dim, act);
+    }
     return ssac_check_launch("ssac_ucb_select");
 }
 
@@ -318,11 +407,19 @@ extern "C" int ssac_act_candidates(const float *outs, int n_actors, int n_rows, 
 
 extern "C" int ssac_act_mean_tanh(const float *const *outs, int n_actors, int64_t ld_out, int n_rows, int act_dim, float *act,
                                   void *stream) {
-    PtrList pl;
-    if (fill_ptrs(pl, outs, n_actors, "ssac_act_mean_tanh: 1..8 actors")) return 1;
     if (n_rows <= 0 || act_dim <= 0 || !act) return ssac_fail("ssac_act_mean_tanh: bad arguments");
     const int n = n_rows * act_dim;
-    SSAC_LAUNCH(mean_tanh_kernel, dim3((n + 255) / 256), dim3(256), 0, ST, pl, n_actors, ld_out, n_rows, act_dim, act);
+    if (n_actors <= ACT_MAX_E) {
+        PtrList<ACT_MAX_E> pl;
+        if (fill_ptrs(pl, outs, n_actors, "ssac_act_mean_tanh: 1..32 actors")) return 1;
+        SSAC_LAUNCH(mean_tanh_kernel<ACT_MAX_E>, dim3((n + 255) / 256), dim3(256), 0, ST, pl, n_actors, ld_out, n_rows, act_dim,
+                    act);
+    } else {
+        PtrList<ACT_MAX_E_WIDE> pl;
+        if (fill_ptrs(pl, outs, n_actors, "ssac_act_mean_tanh: 1..32 actors")) return 1;
+        SSAC_LAUNCH(mean_tanh_kernel<ACT_MAX_E_WIDE>, dim3((n + 255) / 256), dim3(256), 0, ST, pl, n_actors, ld_out, n_rows,
+                    act_dim, act);
+    }
     return ssac_check_launch("ssac_act_mean_tanh");
 }
 
@@ -336,13 +433,30 @@ extern "C" int ssac_act_take_clamp(const float *src, int64_t ld, int col0, int n
 
 extern "C" int ssac_act_discrete(const float *const *outs, int n_actors, int64_t ld_out, int n_rows, int n_actions, int sample,
                                  const ssac_rng *rng, float *act, void *stream) {
-    PtrList pl;
-    if (fill_ptrs(pl, outs, n_actors, "ssac_act_discrete: 1..8 actors")) return 1;
     if (n_rows <= 0 || n_actions <= 0 || n_actions > 64 || !act || (sample && (!rng || n_actors != 1)))
         return ssac_fail("ssac_act_discrete: bad arguments (<= 64 actions; a sample is one actor's and needs an rng stream)");
     RngArgs r{0, nullptr, 0};
     if (rng) r = RngArgs{rng->seed, rng->counter, rng->offset};
-    SSAC_LAUNCH(discrete_act_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_actors, ld_out, n_rows, n_actions, sample,
-                r, act);
+    if (n_actors <= ACT_MAX_E) {
+        PtrList<ACT_MAX_E> pl;
+        if (fill_ptrs(pl, outs, n_actors, "ssac_act_discrete: 1..32 actors")) return 1;
+        SSAC_LAUNCH(discrete_act_kernel<ACT_MAX_E>, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_actors, ld_out, n_rows,
+                    n_actions, sample, r, act);
+    } else {
+        PtrList<ACT_MAX_E_WIDE> pl;
+        if (fill_ptrs(pl, outs, n_actors, "ssac_act_discrete: 1..32 actors")) return 1;
+        SSAC_LAUNCH(discrete_act_kernel<ACT_MAX_E_WIDE>, dim3((n_rows + 63) / 64), dim3(64), 0, ST, pl, n_actors, ld_out, n_rows,
+                    n_actions, sample, r, act);
+    }
     return ssac_check_launch("ssac_act_discrete");
+}
+
+extern "C" int ssac_act_ucb_discrete(const float *logits, const float *q, int n_members, int n_nets, int n_rows, int n_actions,
+                                     float bonus, const ssac_rng *rng, long long member_stride, float *act, void *stream) {
+    if (!logits || !q || !rng || !act || n_members < 2 || n_members > ACT_MAX_E_WIDE || n_nets <= 0 || n_rows <= 0 ||
+        n_actions <= 0 || n_actions > 64)
+        return ssac_fail("ssac_act_ucb_discrete: bad arguments (2..32 members, <= 64 actions, an rng stream)");
+    SSAC_LAUNCH(ucb_discrete_kernel, dim3(n_rows), dim3(64), 0, ST, logits, n_members, n_nets, n_rows, n_actions, q, bonus,
+                RngArgs{rng->seed, rng->counter, rng->offset}, member_stride, act);
+    return ssac_check_launch("ssac_act_ucb_discrete");
 }
