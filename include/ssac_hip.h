@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 8
+#define SSAC_ABI_VERSION 9
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -1103,6 +1103,10 @@ int ssac_act_discrete(const float *const *outs, int n_actors, int64_t ld_out, in
  * One wavefront per row, every reduction in index order: the same bits on every run. */
 int ssac_act_ucb_discrete(const float *logits, const float *q, int n_members, int n_nets, int n_rows, int n_actions,
                           float bonus, const ssac_rng *rng, long long member_stride, float *act, void *stream);
+/* float32 frames of a pixel plan (ABI 9): dst[0, n) = src[0, n), values unchanged -- src = ssac_act_obs (host-written: uncached
+ * or pinned), dst = an ordinary device buffer the recorded encoder's first launch reads.  Recorded in FRONT of the encoder's
+ * launches.  Both pointers 16-byte aligned (16-byte loads and stores, a scalar tail for n % 4 floats); src is only read. */
+int ssac_act_ingest_f32(const float *src, float *dst, int64_t n, void *stream);
 
 /* zero a float buffer (log accumulators) */
 int ssac_zero(float *p, int64_t n, void *stream);

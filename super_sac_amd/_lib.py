@@ -258,6 +258,7 @@ SIGNATURES = {
     "ssac_act_take_clamp": [_P, _L, _I, _I, _I, _F, _F, _P, _P],
     "ssac_act_discrete": [_P, _I, _L, _I, _I, _I, _P, _P, _P],
     "ssac_act_ucb_discrete": [_P, _P, _I, _I, _I, _I, _F, _P, C.c_longlong, _P, _P],
+    "ssac_act_ingest_f32": [_P, _P, _L, _P],
     "ssac_bf16_layout": [_I, _I, _I, C.POINTER(C.c_int64)],
     "ssac_bf16_supported": [_MP],
     "ssac_bf16_sync": [_MP, _P, _P],
@@ -295,7 +296,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def _load():

@@ -1,7 +1,7 @@
 """The acting path as ONE C call per environment step (agent.py:204-315; csrc/ssac_act.hip).
 
-``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent whose networks fit the
-fused MLP kernels take this path: the first call at a given (rule, num_envs) RECORDS the rule's launches -- every actor's
+``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent, or of a pixel-encoder agent
+on uint8 or float32 frames, take this path: the first call at a given (rule, num_envs) RECORDS the rule's launches -- every actor's
 forward (+ tanh-normal sample from the engine's Philox stream, in the kernel), SUNRISE's ensemble-Q passes on the stacked
 candidates, the rule's reduction (UCB arg-max / mean of mean actions / categorical draw / arg-max of mean probabilities) and
 the publish step -- into a launch list of an ``ssac_act`` plan; every later call is ``ssac_act_run``: the observation is
@@ -13,7 +13,16 @@ packed critics' forwards on the state representation and ONE reduction launch (s
 member, the gather, mean + bonus * std, arg-max); their plan is keyed ("sample", n, bonus).  A pack above SSAC_MAX_NETS
 networks is forwarded by several packed launches inside the same list; the reductions take up to 32 members.
 
-What stays on the general path (agent.py's eager code, unchanged): rolling encoders, float-frame observations, injected noise
+Pixel agents: the encoder's launches are recorded in front of the rule's, reading the uint8 frames where the host wrote them.
+With ``acting.FLOAT32_FRAMES = True`` (off by default: float frames then act on the general path, as they always did),
+float32 frames (a frame-stack or normalising wrapper) get a plan of their own, keyed (rule, num_envs, bonus, "float32"): its
+list starts with ssac_act_ingest_f32, which moves the frames out of the host-written buffer for the encoder's first launch.
+``rolling=True`` -- the default of the training loop (main.super_sac, evaluation.run_env) -- is the same call as
+``rolling=False`` for an encoder whose forward_rolling / reset_rolling are the pass-through inherited from ``Encoder`` (this
+package's or the reference's; no shipped encoder overrides them): the plan is not keyed on it, both share one noise stream.
+
+What stays on the general path (agent.py's eager code, unchanged): encoders that override their rolling interface (they keep
+state between calls) under ``rolling=True``, float32 frames unless FLOAT32_FRAMES is set, float64 and other frame dtypes, injected noise
 (a hook on ``rng.draw_normal`` -- the parity tests), ensembles above 32 members, UCB networks outside the fused kernels' shapes
 (hidden > 256), ``from_cpu=False`` callers, Beta actors (beta_dist=True), and every (agent, rule, num_envs) whose recording
 failed once (the call that met the failure included: it is served by the general path, the key is not tried again).  Host RNG contract: the Python ``random`` draws of the reference (``random.choice`` of the
@@ -26,12 +35,13 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, engine, rng
+from . import _lib, engine, nets, rng
 from . import learning_utils as lu
 from ._lib import check, lib
 
 ENABLED = True
-_PLANS = weakref.WeakKeyDictionary()   # agent -> {(rule, num_envs, bonus): _Plan}
+FLOAT32_FRAMES = False                 # record pixel plans for float32 frames as well (off: they act on the general path, as before)
+_PLANS = weakref.WeakKeyDictionary()   # agent -> {(rule, num_envs, bonus) [+ ("float32",) for float frames]: _Plan}
 _FAILED = weakref.WeakKeyDictionary()  # agent -> {plan key}: a recording failed, the general path serves the key from then on
 _SERIAL = [0]
 MAX_MEMBERS = 32                       # SSAC_ACT_MAX_MEMBERS: what the rules' reduction kernels take
@@ -40,15 +50,16 @@ _STREAM_SALT = 0x41C7A11D5EEDB00C      # the acting noise stream: the agent's en
 
 
 class _Plan:
-    def __init__(self, agent, rule, n, dev, pixel_shape=None):
+    def __init__(self, agent, rule, n, dev, pixel_shape=None, pixel_dtype=np.uint8):
         self.rule, self.n, self.dev = rule, n, dev
         self.S = agent.encoder.embedding_dim
-        self.pixel_shape = pixel_shape    # (C, H, W) of a uint8 observation that goes through the pixel encoder, or None
+        self.pixel_shape = pixel_shape    # (C, H, W) of an image observation that goes through the pixel encoder, or None
+        self.obs_dtype = np.dtype(np.float32 if pixel_shape is None else pixel_dtype)   # what the host writes: uint8 / float32 frames
         self.key = agent.encoder.ssac_identity_key if pixel_shape is None else getattr(agent.encoder, "ssac_obs_key", "obs")
         self.discrete = bool(agent.discrete)
         self.A = agent.act_space_size
         self.out_floats = n if self.discrete else n * self.A
-        obs_bytes = 4 * n * self.S if pixel_shape is None else n * int(np.prod(pixel_shape))
+        obs_bytes = 4 * n * self.S if pixel_shape is None else n * int(np.prod(pixel_shape)) * self.obs_dtype.itemsize
         self.handle = lib.ssac_act_create(obs_bytes, self.out_floats)
         if not self.handle:
             raise RuntimeError("libssac_hip: " + lib.ssac_last_error().decode())
@@ -103,18 +114,37 @@ def _conv_module(agent):
 
 
 def _pixel_obs(agent, obs, num_envs):
-    """(key, (C, H, W)) when the observation is a uint8 image batch for a pixel encoder of this package, else None"""
+    """(key, (C, H, W), dtype) when the observation is a uint8 -- with FLOAT32_FRAMES also a float32 -- image batch for a pixel
+    encoder of this package, else None (float64 and every other dtype: the general path)"""
     key = getattr(agent.encoder, "ssac_obs_key", None)
     if key is None:
         return None
     conv = _conv_module(agent)
     v = obs.get(key)
-    if conv is None or not isinstance(v, np.ndarray) or v.dtype != np.uint8:
+    if conv is None or not isinstance(v, np.ndarray) or not (v.dtype == np.uint8 or (FLOAT32_FRAMES and v.dtype == np.float32)):
         return None
     shape = tuple(v.shape[-3:])
     if len(shape) != 3 or v.size != num_envs * int(np.prod(shape)) or shape[0] != conv.conv1.in_channels:
         return None
-    return key, shape
+    return key, shape, v.dtype
+
+
+def _inherits_rolling(cls):
+    """the class's rolling interface is the pass-through it inherited -- forward_rolling = forward, reset_rolling a no-op
+    (nets.Encoder here; nets/__init__.py:26-30 of the reference, for adopted agents: its Encoder is found among the bases by
+    name, the package is not imported) -- i.e. neither function is overridden: the function OBJECTS are compared"""
+    bases = [nets.Encoder] + [b for b in cls.__mro__ if (b.__module__, b.__name__) == ("super_sac.nets", "Encoder")]
+    found = tuple(getattr(cls, name, None) for name in ("forward_rolling", "reset_rolling"))
+    return None not in found and any(found == tuple(b.__dict__.get(name) for name in ("forward_rolling", "reset_rolling"))
+                                     for b in bases)
+
+
+def _rolling_passthrough(enc):
+    """no state between the calls of this encoder: rolling=True computes what rolling=False does (asked once per encoder object)"""
+    if "_ssac_roll_pass" not in enc.__dict__:
+        enc.__dict__["_ssac_roll_pass"] = _inherits_rolling(type(enc)) and "forward_rolling" not in enc.__dict__ \
+            and "reset_rolling" not in enc.__dict__
+    return enc.__dict__["_ssac_roll_pass"]
 
 
 def _eligible(agent, obs, num_envs, sample, rolling):
@@ -124,8 +154,8 @@ def _eligible(agent, obs, num_envs, sample, rolling):
         v = obs.get(agent.encoder.ssac_identity_key)
         if not isinstance(v, np.ndarray) or v.size != num_envs * agent.encoder.embedding_dim:
             return False
-    elif rolling or _pixel_obs(agent, obs, num_envs) is None:
-        return False          # (a rolling encoder keeps state between calls: the general path)
+    elif (rolling and not _rolling_passthrough(agent.encoder)) or _pixel_obs(agent, obs, num_envs) is None:
+        return False          # (an encoder that overrides its rolling interface keeps state between calls: the general path)
     E = len(agent.actors)
     if E > MAX_MEMBERS or agent.act_space_size > 64:
         return False
@@ -252,9 +282,16 @@ def _record_launches(plan, agent, which):
         x_in = plan.obs_dev      # what the actors read: the observation itself, or the encoder's output
         if plan.pixel_shape is not None:
             # the pixel encoder's forward straight from the uint8 observation buffer (the cast and the /255 normalisation
-            # happen in the first layer's patch gather), into a buffer of this plan -- the same launches as lu.encode
+            # happen in the first layer's patch gather), into a buffer of this plan -- the same launches as lu.encode.
+            # float32 frames: one pass (ssac_act_ingest_f32, 16-byte loads and stores) moves them out of the host-written
+            # buffer into a plan-owned one first; the encoder reads that as any float image
             plan.srep = plan.buf(n, S)
-            plan.conv_engine.forward_ptr(plan.obs_dev, (n,) + plan.pixel_shape, 1, plan.srep.data_ptr(), S, False)
+            img_ptr, u8 = plan.obs_dev, 1
+            if plan.obs_dtype == np.float32:
+                plan.frames = plan.buf((n * int(np.prod(plan.pixel_shape)) + 3) // 4 * 4)
+                check(lib.ssac_act_ingest_f32(plan.obs_dev, plan.frames.data_ptr(), n * int(np.prod(plan.pixel_shape)), st))
+                img_ptr, u8 = plan.frames.data_ptr(), 0
+            plan.conv_engine.forward_ptr(img_ptr, (n,) + plan.pixel_shape, u8, plan.srep.data_ptr(), S, False)
             x_in = plan.srep.data_ptr()
         if plan.rule == "forward":
             if E > 1:   # one launch over the packed actors; plan.outs[e] are views of its output
@@ -354,7 +391,11 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
     ucb = bool(sample and agent.ucb_bonus > 0)
     rule = ("ducb" if agent.discrete else "ucb") if ucb else ("sample" if sample else "forward")
     # (the discrete UCB rule is keyed as the sample rule it replaces, told apart by its bonus)
+    # (... and never by `rolling`: a pass-through rolling call is the same call.  float32 frames of a pixel agent: a plan of
+    #  their own beside the uint8 one)
     pkey = ("sample" if rule == "ducb" else rule, num_envs, float(agent.ucb_bonus) if ucb else 0.0)
+    if not lu.is_identity(agent.encoder) and obs[agent.encoder.ssac_obs_key].dtype == np.float32:
+        pkey += ("float32",)
     failed = _FAILED.get(agent)
     if failed and pkey in failed:
         return None
@@ -374,7 +415,7 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
         plans = _PLANS.setdefault(agent, {})
         if len(plans) > 12:
             plans.clear()
-        plan = plans[pkey] = _Plan(agent, rule, num_envs, dev, pixel_shape=None if pix is None else pix[1])
+        plan = plans[pkey] = _Plan(agent, rule, num_envs, dev, *(() if pix is None else pix[1:]))
         plan.conv_engine = eng
         plan.sig = _signature(agent, ucb)   # (binding the arenas may have re-pointed the parameters)
     # the reference's host draws, in its order: random.choice(act_dists) under UCB (for the logged distribution),
@@ -398,7 +439,7 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
             _PLANS.pop(agent, None)
         random.setstate(host_state)
         return None
-    v = np.ascontiguousarray(obs[plan.key], dtype=np.float32 if plan.pixel_shape is None else np.uint8)
+    v = np.ascontiguousarray(obs[plan.key], dtype=plan.obs_dtype)
     rc = lib.ssac_act_run(plan.handle, plan.lists[which], v.ctypes.data, v.nbytes, plan.result.ctypes.data, plan.out_floats,
                           engine.stream())
     if rc:

@@ -257,6 +257,20 @@ __global__ __launch_bounds__(64) void ucb_discrete_kernel(const float *__restric
     if (e == 0) act[b] = (float)best;
 }
 
+// ---- float32 frames of a pixel plan: the host writes them into the plan's observation buffer (uncached device memory behind
+// the large BAR, or pinned host memory); this pass moves them ONCE into an ordinary device buffer, which the recorded
+// encoder's first launch (the patch gather: every pixel is read (k / stride)^2 times) then reads through the caches.  16-byte
+// loads and stores (both pointers 16-byte aligned: checked by the entry point), one lane per 4 floats, grid-stride; the last
+// n % 4 floats by lanes 0..2 of the first workgroup, one float each.  The source is only read.
+__global__ __launch_bounds__(256) void act_ingest_f32_kernel(const float *__restrict__ src, float *__restrict__ dst, int64_t n) {
+    const int64_t n4 = n >> 2;
+    const float4 *s4 = reinterpret_cast<const float4 *>(src);
+    float4 *d4 = reinterpret_cast<float4 *>(dst);
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) d4[i] = s4[i];
+    const int64_t t = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) dst[t] = src[t];
+}
+
 }  // namespace
 
 struct ssac_act {
@@ -459,4 +473,15 @@ extern "C" int ssac_act_ucb_discrete(const float *logits, const float *q, int n_
     SSAC_LAUNCH(ucb_discrete_kernel, dim3(n_rows), dim3(64), 0, ST, logits, n_members, n_nets, n_rows, n_actions, q, bonus,
                 RngArgs{rng->seed, rng->counter, rng->offset}, member_stride, act);
     return ssac_check_launch("ssac_act_ucb_discrete");
+}
+
+// the float32 frames of the observation buffer -> `dst` (n floats, unchanged values): recorded in front of the encoder's
+// launches of a float-frame pixel plan
+extern "C" int ssac_act_ingest_f32(const float *src, float *dst, int64_t n, void *stream) {
+    if (!src || !dst || n <= 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15))
+        return ssac_fail("ssac_act_ingest_f32: bad arguments (n > 0, both pointers 16-byte aligned)");
+    const int64_t blocks = ((n >> 2) + 255) / 256;
+    SSAC_LAUNCH(act_ingest_f32_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks)), dim3(256), 0, ST, src,
+                dst, n);
+    return ssac_check_launch("ssac_act_ingest_f32");
 }
