@@ -507,11 +507,17 @@ __global__ __launch_bounds__(RED_THREADS) void bc_discrete_bwd_kernel(
         const int ai = (int)act[b * ld_act];
         float mx = x[0];
         for (int t = 1; t < A; ++t) mx = fmaxf(mx, x[t]);
-        float se = 0.f;
-        for (int t = 0; t < A; ++t) se += expf(x[t] - mx);
-        const float lse = mx + logf(se);
-        s += (x[ai] - lse) * w;
-        for (int t = 0; t < A; ++t) d_logits[(int64_t)b * A + t] = coef * ((t == ai ? 1.0f : 0.0f) - expf(x[t] - lse));
+        // softmax of the shifted logits; 1 - p of the data action is the sum of the OTHER exponentials over se: a
+        // saturated softmax (p -> 1) loses nothing to cancellation, and no rounding at the magnitude of mx enters
+        float se = 0.f, rest = 0.f;
+        for (int t = 0; t < A; ++t) {
+            const float e = expf(x[t] - mx);
+            se += e;
+            if (t != ai) rest += e;
+        }
+        s += ((x[ai] - mx) - logf(se)) * w;
+        for (int t = 0; t < A; ++t)
+            d_logits[(int64_t)b * A + t] = coef * (t == ai ? rest / se : -(expf(x[t] - mx) / se));
     }
     const float tot = block_reduce<0>(s, scratch);
     if (threadIdx.x == 0) {
