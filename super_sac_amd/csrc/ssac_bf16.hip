@@ -1582,15 +1582,6 @@ void bf_fill(BfArgs &g, const ssac_mlp *nets, const uint16_t *shadow, const int3
     g.xcd = (g_ssac_xcd & 8) ? 0 : 1;   // (ssac_xcd_order bit 3: the chained launches in hardware order)
 }
 
-template <typename K>
-int raise_lds(K kernel, bool &done) {
-    if (done) return 0;
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return ssac_fail("ssac_bf16: cannot raise the dynamic LDS limit");
-    done = true;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int64_t ssac_bf16_layout(int in_dim, int hidden, int out_dim, int64_t offsets[4]) {
@@ -1655,7 +1646,7 @@ extern "C" int ssac_bf16_mlp3_fwd(const ssac_mlp *nets, const uint16_t *shadow, 
         // register-chained form (bf_regchain_kernel): one persistent workgroup per CU, its 8 waves take 32-row units in pairs
         const int per_net = std::max(1, std::min((tiles64 + 7) / 8, 256 / n_sel));
         static bool arc = false;
-        if (raise_lds(bf_regchain_kernel, arc)) return 1;
+        if (ssac_raise_lds(arc, 160 * 1024, "ssac_bf16", bf_regchain_kernel)) return 1;
         SSAC_LAUNCH(bf_regchain_kernel, dim3(per_net, n_sel), dim3(NTHR), RC_LDS, (hipStream_t)stream, g);
         return ssac_check_launch("bf16_mlp3_fwd (register-chained)");
     }
@@ -1666,16 +1657,16 @@ extern "C" int ssac_bf16_mlp3_fwd(const ssac_mlp *nets, const uint16_t *shadow, 
         const int per_net = std::max(1, std::min(tiles64, 256 / n_sel));
         static bool a2 = false, a4 = false;
         if (g.sg.k1p <= 32) {
-            if (raise_lds(bf_stream_kernel<2>, a2)) return 1;
+            if (ssac_raise_lds(a2, 160 * 1024, "ssac_bf16", bf_stream_kernel<2>)) return 1;
             SSAC_LAUNCH(bf_stream_kernel<2>, dim3(per_net, n_sel), dim3(NTHR), lds_s, (hipStream_t)stream, g, tiles64);
         } else {
-            if (raise_lds(bf_stream_kernel<4>, a4)) return 1;
+            if (ssac_raise_lds(a4, 160 * 1024, "ssac_bf16", bf_stream_kernel<4>)) return 1;
             SSAC_LAUNCH(bf_stream_kernel<4>, dim3(per_net, n_sel), dim3(NTHR), lds_s, (hipStream_t)stream, g, tiles64);
         }
         return ssac_check_launch("bf16_mlp3_fwd (stream)");
     }
     static bool attr = false;
-    if (raise_lds(bf_mlp_kernel<MODE_PLAIN>, attr)) return 1;
+    if (ssac_raise_lds(attr, 160 * 1024, "ssac_bf16", bf_mlp_kernel<MODE_PLAIN>)) return 1;
     const size_t lds = bf_lds_bytes(nets->in_dim, nets->hidden, nets->out_dim);
     SSAC_LAUNCH(bf_mlp_kernel<MODE_PLAIN>, dim3((n_rows + TM - 1) / TM, n_sel), dim3(NTHR), lds, (hipStream_t)stream, g);
     return ssac_check_launch("bf16_mlp3_fwd");
@@ -1730,7 +1721,7 @@ extern "C" int ssac_bf16_chain_update(const ssac_mlp *actor, const uint16_t *act
     if (lt > lds) lds = lt;
     if (lc > lds) lds = lc;
     static bool attr = false;
-    if (raise_lds(bf_chain_kernel, attr)) return 1;
+    if (ssac_raise_lds(attr, 160 * 1024, "ssac_bf16", bf_chain_kernel)) return 1;
     const int gx = (n_rows + TM - 1) / TM;
     const int tiles_t = gx * n_sel;
     DeferredLogsArgs dl{};
@@ -1751,7 +1742,7 @@ extern "C" int ssac_bf16_chain_update(const ssac_mlp *actor, const uint16_t *act
         gt.ho = ho;
         if (gather) { gt.gth = *gather; gt.gth_role = 5; }
         static bool attr_pc = false;
-        if (raise_lds(bf_chain_pc_kernel, attr_pc)) return 1;
+        if (ssac_raise_lds(attr_pc, 160 * 1024, "ssac_bf16", bf_chain_pc_kernel)) return 1;
         SSAC_LAUNCH(bf_chain_pc_kernel, dim3(gx + tiles_t + gx * critics->n_nets + dl_on), dim3(NTHR), lds, (hipStream_t)stream,
                     ga, gt, gc, gx, tiles_t, gx, dl, dl_on);
         return ssac_check_launch("bf16_chain_pc");
@@ -1816,7 +1807,7 @@ extern "C" int ssac_bf16_wgrad_lossfold(const ssac_mlp *nets, uint16_t *shadow, 
     }
     const size_t lds = sizeof(float) * (g.bp + 16);
     static bool attr = false;
-    if (raise_lds(bf_wgrad_kernel, attr)) return 1;
+    if (ssac_raise_lds(attr, 160 * 1024, "ssac_bf16", bf_wgrad_kernel)) return 1;
     SSAC_LAUNCH(bf_wgrad_kernel, dim3((g.tiles2 + g.tiles1 + 1) * nets->n_nets), dim3(256), lds, (hipStream_t)stream, g);
     return ssac_check_launch("bf16_wgrad");
 }

@@ -1106,11 +1106,8 @@ extern "C" int ssac_conv_fwd(const float *x, const float *w, const float *bias, 
     const int n_tiles = (int)((M + CV_PIX - 1) / CV_PIX);
     const size_t lds = sizeof(float) * (size_t)k * k * (ci / 32) * 32 * WL_LD;
     if (lds > 160 * 1024) return ssac_fail("ssac_conv_fwd: weight tile does not fit LDS");
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)conv_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    static bool attr = false;   // (a refused limit is left to the launch check below, here as in every launcher of this file)
+    (void)ssac_raise_lds(attr, 160 * 1024, "conv_fwd", conv_fwd_kernel);
     const int per_cu = persistent_per_cu(lds);
     const int cap = 256 * per_cu / (co / 32) > 0 ? 256 * per_cu / (co / 32) : 1;
     const int gx = n_tiles < cap ? n_tiles : cap;
@@ -1129,11 +1126,7 @@ extern "C" int ssac_conv_dgrad(const float *dy, const float *w, const float *x_m
     const size_t lds = sizeof(float) * (size_t)k * k * (co / 32) * 32 * WL_LD;
     if (lds > 160 * 1024) return ssac_fail("ssac_conv_dgrad: weight tile does not fit LDS");
     static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)conv_dgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)conv_dgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    (void)ssac_raise_lds(attr, 160 * 1024, "conv_dgrad", conv_dgrad_kernel<true>, conv_dgrad_kernel<false>);
     const int per_cu = persistent_per_cu(lds);
     const int cap = 256 * per_cu / (ci / 32) > 0 ? 256 * per_cu / (ci / 32) : 1;
     const int gx = n_tiles < cap ? n_tiles : cap;
@@ -1153,11 +1146,7 @@ extern "C" int ssac_conv_dgrad(const float *dy, const float *w, const float *x_m
         const int tj = (k + s - 1) / s, max_chunks = tj * tj * (co / 32);   // taps of the richest class
         const size_t lds2 = sizeof(float) * (size_t)max_chunks * 32 * WL_LD + sizeof(int) * 128;
         static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void *)conv_dgrad_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-            attr2 = true;
-        }
+        (void)ssac_raise_lds(attr2, 160 * 1024, "conv_dgrad_strided", conv_dgrad_strided_kernel);
         if (lds2 > 160 * 1024) return ssac_fail("ssac_conv_dgrad: weight tile does not fit LDS");
         // persistent workgroups, the same number for every class
         const int per_cu2 = persistent_per_cu(lds2), ncls = s * s;
@@ -1208,10 +1197,7 @@ extern "C" int ssac_conv_wgrad_img(const float *dy, const float *x, float *parti
     g.x = x; g.dy = dy; g.B = B; g.Hi = Hi; g.Wi = Wi; g.ci = ci; g.co = co; g.k = k; g.s = s;
     g.Ho = (Hi - k) / s + 1; g.Wo = (Wi - k) / s + 1;
     static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)conv_wgrad_img_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    (void)ssac_raise_lds(attr, 160 * 1024, "conv_wgrad_img", conv_wgrad_img_kernel);
     SSAC_LAUNCH(conv_wgrad_img_kernel, dim3(slices, ci / 32, co / 32), dim3(CV_THREADS), lds, (hipStream_t)stream, g, partial_w,
                 partial_b);
     return ssac_check_launch("conv_wgrad_img");
@@ -1255,11 +1241,7 @@ extern "C" int ssac_conv_first_fwd(const float *img, const float *w, const float
     const int n_tiles = (M + CV_PIX - 1) / CV_PIX;
     const size_t lds = sizeof(float) * (size_t)C * k * 32 * 2 * kh;
     static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)conv_first_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)conv_first_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    (void)ssac_raise_lds(attr, 160 * 1024, "conv_first_fwd", conv_first_fwd_kernel<2>, conv_first_fwd_kernel<4>);
     if (lds > 160 * 1024) return ssac_fail("ssac_conv_first_fwd: weight tile does not fit LDS");
     const int cap = 1024 / (co / 32) > 0 ? 1024 / (co / 32) : 1;  // persistent: ~4 workgroups per CU in total
     const int gx = n_tiles < cap ? n_tiles : cap;
@@ -1324,7 +1306,7 @@ extern "C" int ssac_conv_first_wgrad_band(const float *dy, const float *img, flo
 #define SSAC_FIRST_WGRAD_BAND(NB) \
     case NB: { \
         static bool attr##NB = false; \
-        if (!attr##NB) { (void)hipFuncSetAttribute((const void *)conv_first_wgrad_band_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr##NB = true; } \
+        (void)ssac_raise_lds(attr##NB, 160 * 1024, "conv_first_wgrad_band", conv_first_wgrad_band_kernel<NB>); \
         SSAC_LAUNCH(conv_first_wgrad_band_kernel<NB>, grid, block, lds, (hipStream_t)stream, g, R, n_items, partial_w, partial_b); } break;
     switch (nb) {
         SSAC_FIRST_WGRAD_BAND(1) SSAC_FIRST_WGRAD_BAND(2) SSAC_FIRST_WGRAD_BAND(3) SSAC_FIRST_WGRAD_BAND(4)

@@ -1894,10 +1894,15 @@ size_t fused_lds_bytes(int in_dim, int hidden, int out_dim, int tm = TM, bool db
 // staging; 17 = 16 rows, single staging buffer (wide input + wide head shapes need it).
 struct TileChoice { int tm; int variant; };  // variant 0 double-buffered staging, 1 single buffer
 
-TileChoice choose_tile(const FusedArgs &g, int n_sel) {
-    const bool fits32 = fused_lds_bytes(g.in_dim, g.hidden, g.out_dim, 32) <= 160 * 1024;
+size_t fused_lds_bytes(const ssac_mlp *n, int tm, bool dbuf = true, bool w3_late = false, bool co = false, int cons_wa = 0) {
+    return fused_lds_bytes(n->in_dim, n->hidden, n->out_dim, tm, dbuf, w3_late, co, cons_wa);
+}
+size_t max_lds(size_t a, size_t b, size_t c = 0) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+
+TileChoice choose_tile(int in_dim, int hidden, int out_dim, int n_rows, int n_sel) {
+    const bool fits32 = fused_lds_bytes(in_dim, hidden, out_dim, 32) <= 160 * 1024;
     // a wide input together with a wide head (e.g. 376 -> 34): only the single-buffer carve fits
-    if (fused_lds_bytes(g.in_dim, g.hidden, g.out_dim, 16) > 160 * 1024) return {16, 1};
+    if (fused_lds_bytes(in_dim, hidden, out_dim, 16) > 160 * 1024) return {16, 1};
     switch (g_tile_rows) {
         case 17: return {16, 1};
         case 16: return {16, 0};
@@ -1906,25 +1911,29 @@ TileChoice choose_tile(const FusedArgs &g, int n_sel) {
     }
     // automatic: 16-row tiles while the launch still fits the chip in one round (one workgroup per CU), and
     // whenever wide inputs / heads leave no room for 32 rows in the 160 KB of LDS
-    const int wg16 = ((g.n_rows + 15) / 16) * n_sel;
+    const int wg16 = ((n_rows + 15) / 16) * n_sel;
     return {(wg16 <= 256 || !fits32) ? 16 : 32, 0};
+}
+TileChoice choose_tile(const FusedArgs &g, int n_sel) { return choose_tile(g.in_dim, g.hidden, g.out_dim, g.n_rows, n_sel); }
+TileChoice choose_tile(const ssac_mlp *n, int n_rows, int n_sel) {
+    return choose_tile(n->in_dim, n->hidden, n->out_dim, n_rows, n_sel);
 }
 
 bool fused_ok(const ssac_mlp *n) {
     return n && n->hidden % 32 == 0 && n->hidden <= 256 && n->out_dim >= 1 && n->out_dim <= HEAD_MAX &&
-           n->in_dim >= 1 && fused_lds_bytes(n->in_dim, n->hidden, n->out_dim, 16, false) <= 160 * 1024;
+           n->in_dim >= 1 && fused_lds_bytes(n, 16, false) <= 160 * 1024;
 }
 
 // the actor pass with a double-buffered K loop and the head's rows parked in staging buffer 1 (W3LATE): for actors whose
 // resident head image leaves no room for the second buffer
 bool fused_dbuf_late_ok(const ssac_mlp *n) {
     return fused_ok(n) && (size_t)n->out_dim * (n->hidden + APAD) <= (size_t)WS_FLOATS &&
-           fused_lds_bytes(n->in_dim, n->hidden, n->out_dim, 16, true, true) <= 160 * 1024;
+           fused_lds_bytes(n, 16, true, true) <= 160 * 1024;
 }
 
 // the merged launches run their critic halves with double-buffered staging only
 bool fused_dbuf_ok(const ssac_mlp *n) {
-    return fused_ok(n) && fused_lds_bytes(n->in_dim, n->hidden, n->out_dim, 16, true) <= 160 * 1024;
+    return fused_ok(n) && fused_lds_bytes(n, 16, true) <= 160 * 1024;
 }
 
 void fill_common(FusedArgs &g, const ssac_mlp *nets, const int32_t *ids, const float *X, int64_t ldx,
@@ -1936,16 +1945,104 @@ void fill_common(FusedArgs &g, const ssac_mlp *nets, const int32_t *ids, const f
     g.dbg = g_fused_dbg; g.tl = g_ssac_timeline; g.xcd = g_ssac_xcd & 1;
 }
 
+int fail_for(const char *who, const char *what) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return ssac_fail(msg);
+}
+
+// the tanh-normal sample of an actor pass: its noise (eps, or the rng stream) and where the action and log pi go
+void fill_sample(FusedArgs &g, const float *eps, float lo, float hi, const ssac_rng *rng, float *act_dst, int64_t ld_act,
+                 int64_t act_col0, float *logp) {
+    g.eps = eps; g.lo = lo; g.hi = hi;
+    if (rng) g.rng = RngArgs{rng->seed, rng->counter, rng->offset};
+    g.act_dst = act_dst; g.ld_act = ld_act; g.act_col0 = act_col0; g.logp = logp;
+}
+
+// the loss side of a critic pass; refuses (the launcher's last check) when neither form of the TD target is given
+int fill_loss(const char *who, FusedArgs &g, const float *td, const float *weight, const float *act, int64_t ld_act,
+              const ssac_popart *popart, int pop, float denom, float *DQ, float *DZ2, float *DZ1, float *partials,
+              const ssac_td_spec *lazy_td) {
+    g.td = td; g.weight = weight; g.act = act; g.ld_a = ld_act; g.popart = popart; g.pop = pop;
+    g.denom = denom; g.DQ = DQ; g.DZ2 = DZ2; g.DZ1 = DZ1; g.partials = partials;
+    if (lazy_td) g.tds = *lazy_td;
+    if (!td && !lazy_td) return fail_for(who, "no TD target given");
+    return 0;
+}
+
+// The in-launch gather of a merged launch: checked against the networks, then handed to the actor's pass (role 1) and the
+// online critics' (role 2).  x1sa: the launcher's own [s'|a'] buffer when the gather has to fill that very buffer (the
+// chain), else null.  Without a gather the two passes read Xa / Xc (ga.X, gc.X), which must then be there.
+int bind_gather(const char *who, const ssac_gather *gather, const ssac_mlp *actor, const ssac_mlp *critics,
+                const float *x1sa, FusedArgs &ga, FusedArgs &gc) {
+    if (!gather) return (ga.X && gc.X) ? 0 : fail_for(who, "Xa / Xc missing");
+    if (gather->s_elems != actor->in_dim || gather->s_elems + gather->a_elems != critics->in_dim)
+        return fail_for(who, "gather sizes do not match the networks");
+    if (!gather->s || !gather->s1 || !gather->act || !gather->rew || !gather->done || !gather->xsa ||
+        (x1sa ? gather->x1sa != x1sa : !gather->x1sa) || !gather->rew_out || !gather->done_out ||
+        (!gather->idx && !gather->feed))
+        return fail_for(who, "incomplete ssac_gather");
+    if (gather->feed && gather->n_logs > NTHR) return fail_for(who, "log block too large");
+    ga.gth = *gather; ga.gth_role = 1;
+    gc.gth = *gather; gc.gth_role = 2;
+    return 0;
+}
+
+DeferredLogsArgs deferred_args(const ssac_deferred_logs *d) {
+    return DeferredLogsArgs{d->partials, d->n_nets, d->sumsq, d->n_ss, d->td_stats, d->td_off, d->n_rows, d->denom, d->feed};
+}
+
+// behind the SSAC_LAUNCH of a merged kernel that gathers from the input ring: its first n_args arguments are FusedArgs
+// whose slot_now a replay through ssac_step_run fills in
+void patch_slots(int n_args) {
+    for (int a = 0; a < n_args; ++a) ssac_record_slot_patch(a, offsetof(FusedArgs, slot_now));
+}
+
+// The instantiations of one kernel template that a launcher chooses from, keyed by (tile rows, form).  The table is the one
+// place that names them: pick() raises the dynamic-LDS limit of ALL of them on the family's first launch and hands out the
+// one asked for (null + ssac_fail otherwise) -- no instantiation can be launched without having had its limit raised.
+enum { FORM_SINGLE = 0, FORM_DBUF = 1, FORM_LATE = 2 };   // the actor half's weight staging (FORM_LATE: W3LATE, fused_mlp_body)
+template <typename... A>
+struct KernelFamily {
+    using Fn = void (*)(A...);
+    struct Arm { int tm, form; Fn fn; };
+    const char *name;
+    std::vector<Arm> arms;
+    bool raised = false;
+    Fn pick(int tm, int form) {
+        if (!raised) {
+            std::vector<const void *> ks;
+            for (const Arm &a : arms) ks.push_back((const void *)a.fn);
+            if (ssac_raise_lds(raised, ks.data(), ks.size(), 160 * 1024, name)) return nullptr;
+        }
+        for (const Arm &a : arms)
+            if (a.tm == tm && a.form == form) return a.fn;
+        ssac_fail("ssac_fused: no kernel instantiation for this tile / form");
+        return nullptr;
+    }
+};
+KernelFamily<FusedArgs, FusedArgs, int, int, int> DUAL2{"fused_dual2", {   // (target tile rows, CRITIC tile rows)
+    {16, 16, fused_dual2_kernel<16, 16>}, {16, 32, fused_dual2_kernel<16, 32>},
+    {32, 16, fused_dual2_kernel<32, 16>}, {32, 32, fused_dual2_kernel<32, 32>}}};
+KernelFamily<FusedArgs, FusedArgs, int, int> DUAL{"fused_dual", {
+    {16, FORM_DBUF, fused_dual_kernel<16, true>}, {32, FORM_DBUF, fused_dual_kernel<32, true>},
+    {16, FORM_SINGLE, fused_dual_kernel<16, false>}, {32, FORM_SINGLE, fused_dual_kernel<32, false>}}};
+KernelFamily<FusedArgs, FusedArgs, FusedArgs, FusedArgs, int, int, int, DeferredLogsArgs, int> CHAIN{"fused_chain", {
+    {16, FORM_DBUF, fused_chain_kernel<16, true>}, {32, FORM_DBUF, fused_chain_kernel<32, true>},
+    {16, FORM_SINGLE, fused_chain_kernel<16, false>}, {32, FORM_SINGLE, fused_chain_kernel<32, false>}}};
+KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int, int, int, DeferredLogsArgs, int, XchgArgs, int> CHAIN_PC{"fused_chain_pc", {
+    {16, FORM_DBUF, fused_chain_pc_kernel<16, true>}, {32, FORM_DBUF, fused_chain_pc_kernel<32, true>},
+    {16, FORM_SINGLE, fused_chain_pc_kernel<16, false>}, {32, FORM_SINGLE, fused_chain_pc_kernel<32, false>},
+    {16, FORM_LATE, fused_chain_pc_kernel<16, true, true>}, {32, FORM_LATE, fused_chain_pc_kernel<32, true, true>}}};
+KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int> ACTOR_CHAIN{"fused_actor_chain", {
+    {16, FORM_DBUF, fused_actor_chain_kernel<16>}, {32, FORM_DBUF, fused_actor_chain_kernel<32>},
+    {16, FORM_SINGLE, fused_actor_chain_kernel<16, false>}, {32, FORM_SINGLE, fused_actor_chain_kernel<32, false>}}};
+
 template <int MODE, int TMR, bool DBUF>
 int launch_fused_t(const FusedArgs &g, int n_sel, hipStream_t st) {
-    static bool attr_set = false;
+    static bool raised = false;
     const size_t lds = fused_lds_bytes(g.in_dim, g.hidden, g.out_dim, TMR, DBUF);
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)fused_mlp_kernel<MODE, TMR, DBUF>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return ssac_fail("fused_mlp: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    if (ssac_raise_lds(raised, 160 * 1024, "fused_mlp", fused_mlp_kernel<MODE, TMR, DBUF>)) return 1;
     dim3 grid((g.n_rows + TMR - 1) / TMR, n_sel);
     SSAC_LAUNCH((fused_mlp_kernel<MODE, TMR, DBUF>), grid, dim3(NTHR), lds, st, g);
     return ssac_check_launch("fused_mlp");
@@ -2007,9 +2104,7 @@ extern "C" int ssac_actor_sample_fused(const ssac_mlp *actor, const float *X, in
     FusedArgs g{};
     fill_common(g, actor, nullptr, X, ldx, 0, n_rows);
     g.H1 = H1; g.H2 = H2; g.Y = out;
-    g.eps = eps; g.lo = log_std_lo; g.hi = log_std_hi;
-    if (rng) g.rng = RngArgs{rng->seed, rng->counter, rng->offset};
-    g.act_dst = act_dst; g.ld_act = ld_act; g.act_col0 = act_col0; g.logp = logp;
+    fill_sample(g, eps, log_std_lo, log_std_hi, rng, act_dst, ld_act, act_col0, logp);
     return launch_fused<MODE_SAMPLE>(g, 1, (hipStream_t)stream);
 }
 
@@ -2026,9 +2121,8 @@ extern "C" int ssac_actor_sample_concat_fused(const ssac_mlp *actor, const float
     FusedArgs g{};
     fill_common(g, actor, nullptr, X, ldx, 0, n_rows);
     g.H1 = H1; g.H2 = H2; g.Y = out;
-    g.eps = eps; g.lo = log_std_lo; g.hi = log_std_hi;
-    if (rng) g.rng = RngArgs{rng->seed, rng->counter, rng->offset};
-    g.act_dst = xsa; g.ld_act = ld_xsa; g.act_col0 = actor->in_dim; g.logp = logp; g.copy_x = 1;
+    fill_sample(g, eps, log_std_lo, log_std_hi, rng, xsa, ld_xsa, actor->in_dim, logp);
+    g.copy_x = 1;
     return launch_fused<MODE_SAMPLE>(g, 1, (hipStream_t)stream);
 }
 
@@ -2050,25 +2144,12 @@ extern "C" int ssac_target_fwd_critic_bwdu(const ssac_mlp *targets, const int32_
     gc.act = act; gc.ld_a = ld_act; gc.DZ2 = DZ2u; gc.DZ1 = DZ1u;
     const int tt = choose_tile(gt, n_sel).tm, tc = choose_tile(gc, critics->n_nets).tm;
     const int tgx = (n_rows + tt - 1) / tt, cgx = (n_rows + tc - 1) / tc;
-    size_t lds = fused_lds_bytes(targets->in_dim, targets->hidden, targets->out_dim, tt, true);
-    const size_t lc = fused_lds_bytes(critics->in_dim, critics->hidden, critics->out_dim, tc, true);
-    if (lc > lds) lds = lc;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *ks[4] = {(const void *)fused_dual2_kernel<16, 16>, (const void *)fused_dual2_kernel<16, 32>,
-                             (const void *)fused_dual2_kernel<32, 16>, (const void *)fused_dual2_kernel<32, 32>};
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return ssac_fail("fused_dual2: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    const size_t lds = max_lds(fused_lds_bytes(targets, tt), fused_lds_bytes(critics, tc));
+    const auto kernel = DUAL2.pick(tt, tc);
+    if (!kernel) return 1;
     const int tiles_t = tgx * n_sel;
     const dim3 grid(tiles_t + cgx * critics->n_nets);
-    hipStream_t st = (hipStream_t)stream;
-    if (tt == 16 && tc == 16) SSAC_LAUNCH((fused_dual2_kernel<16, 16>), grid, dim3(NTHR), lds, st, gt, gc, tiles_t, tgx, cgx);
-    else if (tt == 16) SSAC_LAUNCH((fused_dual2_kernel<16, 32>), grid, dim3(NTHR), lds, st, gt, gc, tiles_t, tgx, cgx);
-    else if (tc == 16) SSAC_LAUNCH((fused_dual2_kernel<32, 16>), grid, dim3(NTHR), lds, st, gt, gc, tiles_t, tgx, cgx);
-    else SSAC_LAUNCH((fused_dual2_kernel<32, 32>), grid, dim3(NTHR), lds, st, gt, gc, tiles_t, tgx, cgx);
+    SSAC_LAUNCH(kernel, grid, dim3(NTHR), lds, (hipStream_t)stream, gt, gc, tiles_t, tgx, cgx);
     return ssac_check_launch("fused_dual2");
 }
 
@@ -2084,46 +2165,19 @@ extern "C" int ssac_actor_sample_critic_fwd(const ssac_mlp *actor, const float *
     if (n_rows <= 0) return 0;
     FusedArgs ga{}, gc{};
     fill_common(ga, actor, nullptr, Xa, ldxa, 0, n_rows);
-    ga.eps = eps; ga.lo = log_std_lo; ga.hi = log_std_hi;
-    if (rng) ga.rng = RngArgs{rng->seed, rng->counter, rng->offset};
-    ga.act_dst = act_dst; ga.ld_act = ld_act; ga.act_col0 = act_col0; ga.logp = logp;
+    fill_sample(ga, eps, log_std_lo, log_std_hi, rng, act_dst, ld_act, act_col0, logp);
     fill_common(gc, critics, nullptr, Xc, ldxc, 0, n_rows);
     gc.H1 = H1; gc.H2 = H2; gc.Y = Q;
-    if (gather) {
-        if (gather->s_elems != actor->in_dim || gather->s_elems + gather->a_elems != critics->in_dim)
-            return ssac_fail("ssac_actor_sample_critic_fwd: gather sizes do not match the networks");
-        if (!gather->s || !gather->s1 || !gather->act || !gather->rew || !gather->done || !gather->xsa ||
-            !gather->x1sa || !gather->rew_out || !gather->done_out || (!gather->idx && !gather->feed))
-            return ssac_fail("ssac_actor_sample_critic_fwd: incomplete ssac_gather");
-        if (gather->feed && gather->n_logs > NTHR) return ssac_fail("ssac_actor_sample_critic_fwd: log block too large");
-        ga.gth = *gather; ga.gth_role = 1;
-        gc.gth = *gather; gc.gth_role = 2;
-    } else if (!Xa || !Xc) {
-        return ssac_fail("ssac_actor_sample_critic_fwd: Xa / Xc missing");
-    }
+    if (bind_gather("ssac_actor_sample_critic_fwd", gather, actor, critics, nullptr, ga, gc)) return 1;
     const int tc = choose_tile(gc, critics->n_nets).tm;  // what a stand-alone forward of the critics would use
     const int tiles_a = (n_rows + 15) / 16, cgx = (n_rows + tc - 1) / tc;
     const bool adbuf = fused_dbuf_ok(actor);
-    size_t lds = fused_lds_bytes(actor->in_dim, actor->hidden, actor->out_dim, 16, adbuf);
-    const size_t lc = fused_lds_bytes(critics->in_dim, critics->hidden, critics->out_dim, tc, true);
-    if (lc > lds) lds = lc;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *ks[4] = {(const void *)fused_dual_kernel<16, true>, (const void *)fused_dual_kernel<32, true>,
-                             (const void *)fused_dual_kernel<16, false>, (const void *)fused_dual_kernel<32, false>};
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return ssac_fail("fused_dual: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    const size_t lds = max_lds(fused_lds_bytes(actor, 16, adbuf), fused_lds_bytes(critics, tc));
+    const auto kernel = DUAL.pick(tc, adbuf ? FORM_DBUF : FORM_SINGLE);
+    if (!kernel) return 1;
     const dim3 grid(tiles_a + cgx * critics->n_nets);
-    hipStream_t st = (hipStream_t)stream;
-    if (tc == 16 && adbuf) SSAC_LAUNCH((fused_dual_kernel<16, true>), grid, dim3(NTHR), lds, st, ga, gc, tiles_a, cgx);
-    else if (adbuf) SSAC_LAUNCH((fused_dual_kernel<32, true>), grid, dim3(NTHR), lds, st, ga, gc, tiles_a, cgx);
-    else if (tc == 16) SSAC_LAUNCH((fused_dual_kernel<16, false>), grid, dim3(NTHR), lds, st, ga, gc, tiles_a, cgx);
-    else SSAC_LAUNCH((fused_dual_kernel<32, false>), grid, dim3(NTHR), lds, st, ga, gc, tiles_a, cgx);
-    if (gather && gather->feed)
-        for (int a = 0; a < 2; ++a) ssac_record_slot_patch(a, offsetof(FusedArgs, slot_now));   // ga, gc
+    SSAC_LAUNCH(kernel, grid, dim3(NTHR), lds, (hipStream_t)stream, ga, gc, tiles_a, cgx);
+    if (gather && gather->feed) patch_slots(2);   // ga, gc
     return ssac_check_launch("fused_dual");
 }
 
@@ -2151,26 +2205,13 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
     if (n_rows <= 0) return 0;
     FusedArgs ga{}, gr{}, gt{}, gc{};
     fill_common(ga, actor, nullptr, Xa, ldxa, 0, n_rows);
-    ga.eps = eps; ga.lo = log_std_lo; ga.hi = log_std_hi;
-    if (rng) ga.rng = RngArgs{rng->seed, rng->counter, rng->offset};
-    ga.act_dst = x1sa; ga.ld_act = ld_x1; ga.act_col0 = act_col0; ga.logp = logp;
+    fill_sample(ga, eps, log_std_lo, log_std_hi, rng, x1sa, ld_x1, act_col0, logp);
     fill_common(gt, targets, net_ids, x1sa, ld_x1, 0, n_rows);
     gt.Y = Qt;
     fill_common(gc, critics, nullptr, Xc, ldxc, 0, n_rows);
     gc.H1 = H1; gc.H2 = H2; gc.Y = Q; gc.DZ2 = DZ2u; gc.DZ1 = DZ1u; gc.W3S = DZ2u ? nullptr : W3_snapshot;
     gc.xcd = ((g_ssac_xcd & 1) || !(g_ssac_xcd & 8)) ? 1 : 0;   // the chained launch: XCD-contiguous halves by default
-    if (gather) {
-        if (gather->s_elems != actor->in_dim || gather->s_elems + gather->a_elems != critics->in_dim)
-            return ssac_fail("ssac_chain_update: gather sizes do not match the networks");
-        if (!gather->s || !gather->s1 || !gather->act || !gather->rew || !gather->done || !gather->xsa ||
-            gather->x1sa != x1sa || !gather->rew_out || !gather->done_out || (!gather->idx && !gather->feed))
-            return ssac_fail("ssac_chain_update: incomplete ssac_gather");
-        if (gather->feed && gather->n_logs > NTHR) return ssac_fail("ssac_chain_update: log block too large");
-        ga.gth = *gather; ga.gth_role = 1;
-        gc.gth = *gather; gc.gth_role = 2;
-    } else if (!Xa || !Xc) {
-        return ssac_fail("ssac_chain_update: Xa / Xc missing");
-    }
+    if (bind_gather("ssac_chain_update", gather, actor, critics, x1sa, ga, gc)) return 1;
     gr = ga;
     if (gather) gr.gth_role = 3;
     if (gather && gather->feed && gather->ids_word >= 0) { gt.gth = *gather; gt.gth_role = 4; }
@@ -2182,36 +2223,22 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
     const int A_ = actor->out_dim / 2;
     const bool pc_form = handoff && A_ <= 32 && targets->hidden * A_ <= NTHR * HANDOFF_MAX_WA;
     const bool alate = pc_form && !adbuf && fused_dbuf_late_ok(actor);
-    size_t lds = fused_lds_bytes(actor->in_dim, actor->hidden, actor->out_dim, 16, adbuf || alate, alate);
-    const size_t lt = fused_lds_bytes(targets->in_dim, targets->hidden, targets->out_dim, 16, true);
-    const size_t lc = fused_lds_bytes(critics->in_dim, critics->hidden, critics->out_dim, tc, true);
-    if (lt > lds) lds = lt;
-    if (lc > lds) lds = lc;
+    const size_t lds = max_lds(fused_lds_bytes(actor, 16, adbuf || alate, alate), fused_lds_bytes(targets, 16),
+                               fused_lds_bytes(critics, tc));
     if (lds > 160 * 1024) return ssac_fail("ssac_chain_update: LDS carve does not fit");
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *ks[4] = {(const void *)fused_chain_kernel<16, true>, (const void *)fused_chain_kernel<32, true>,
-                             (const void *)fused_chain_kernel<16, false>, (const void *)fused_chain_kernel<32, false>};
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return ssac_fail("fused_chain: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    const auto chain_kernel = CHAIN.pick(tc, adbuf ? FORM_DBUF : FORM_SINGLE);
+    if (!chain_kernel) return 1;
     const int tiles_t = tgx * n_sel;
-    DeferredLogsArgs dl{};
     const int dl_on = (deferred && deferred->feed) ? 1 : 0;
-    if (dl_on)
-        dl = DeferredLogsArgs{deferred->partials, deferred->n_nets, deferred->sumsq, deferred->n_ss, deferred->td_stats,
-                              deferred->td_off, deferred->n_rows, deferred->denom, deferred->feed};
+    const DeferredLogsArgs dl = dl_on ? deferred_args(deferred) : DeferredLogsArgs{};
     hipStream_t st = (hipStream_t)stream;
     // Co-resident form (fused_chain_co_kernel): when 16-row tiles of the three roles make MORE than one workgroup per CU but
     // at most two, and each role's co-resident carve fits half a CU's LDS.  (Launches of <= 256 16-row tiles are one round
     // at one workgroup per CU already and keep the double-buffered K loop.)
-    const int n16 = tgx + tgx * n_sel + tgx * critics->n_nets + ((deferred && deferred->feed) ? 1 : 0);
-    const size_t co_lds_a = fused_lds_bytes(actor->in_dim, actor->hidden, actor->out_dim, 16, false, false, true);
-    const size_t co_lds_t = fused_lds_bytes(targets->in_dim, targets->hidden, targets->out_dim, 16, false, false, true, targets->hidden * A_);
-    const size_t co_lds_c = fused_lds_bytes(critics->in_dim, critics->hidden, critics->out_dim, 16, false, false, true);
-    const size_t co_lds = co_lds_a > co_lds_t ? (co_lds_a > co_lds_c ? co_lds_a : co_lds_c) : (co_lds_t > co_lds_c ? co_lds_t : co_lds_c);
+    const int n16 = tgx + tgx * n_sel + tgx * critics->n_nets + dl_on;
+    const size_t co_lds = max_lds(fused_lds_bytes(actor, 16, false, false, true),
+                                  fused_lds_bytes(targets, 16, false, false, true, targets->hidden * A_),
+                                  fused_lds_bytes(critics, 16, false, false, true));
     const bool co_form = pc_form && g_chain_form == 1 && g_tile_rows == 0 && target_splits == 1 && n16 > 256 && n16 <= 512 &&
                          co_lds <= 80 * 1024;
     // RESIDENCY INVARIANT of the hand-off launches (any B x N, any number of rounds of workgroups): a consumer spins on granules
@@ -2235,16 +2262,8 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
         ga.ho = ho;
         gt.ho = ho;
         if (gather) { gt.gth = *gather; gt.gth_role = 5; }
-        static bool pc_attr = false;
-        if (!pc_attr) {
-            const void *ks[6] = {(const void *)fused_chain_pc_kernel<16, true>, (const void *)fused_chain_pc_kernel<32, true>,
-                                 (const void *)fused_chain_pc_kernel<16, false>, (const void *)fused_chain_pc_kernel<32, false>,
-                                 (const void *)fused_chain_pc_kernel<16, true, true>, (const void *)fused_chain_pc_kernel<32, true, true>};
-            for (const void *k : ks)
-                if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return ssac_fail("fused_chain_pc: cannot raise the dynamic LDS limit");
-            pc_attr = true;
-        }
+        const auto pc_kernel = CHAIN_PC.pick(tc, alate ? FORM_LATE : adbuf ? FORM_DBUF : FORM_SINGLE);
+        if (!pc_kernel) return 1;
         const int tiles_c = tiles_t * target_splits;   // consumers: one per (slot, column split, tile)
         // critic-sharded rank: the exchange of the subset's target Q as a tail workgroup of THIS launch (xchg != NULL)
         XchgArgs xa{};
@@ -2258,41 +2277,26 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
             xchg_on = 1;
         }
         if (co_form) {
-            static bool co_attr = false;
-            if (!co_attr) {
-                if (hipFuncSetAttribute((const void *)fused_chain_co_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-                    return ssac_fail("fused_chain_co: cannot raise the dynamic LDS limit");
-                co_attr = true;
-            }
+            static bool co_raised = false;
+            if (ssac_raise_lds(co_raised, 80 * 1024, "fused_chain_co", fused_chain_co_kernel)) return 1;
             const dim3 grid_co(tgx + tiles_t + tgx * critics->n_nets + dl_on);
 #if defined(SSAC_LAB) && defined(SSAC_EXP_NO_STORE)
             gc.H1 = gc.H2 = gc.DZ1 = gc.DZ2 = gc.Y = gc.W3S = nullptr;   // (experiment build: the critic tiles store nothing)
 #endif
             SSAC_LAUNCH(fused_chain_co_kernel, grid_co, dim3(NTHR), co_lds, st, ga, gt, gc, tgx, tiles_t, tgx, tgx, dl, dl_on);
-            if (gather && gather->feed)
-                for (int a = 0; a < 3; ++a) ssac_record_slot_patch(a, offsetof(FusedArgs, slot_now));   // ga, gt, gc
+            if (gather && gather->feed) patch_slots(3);   // ga, gt, gc
             return ssac_check_launch("fused_chain_co");
         }
         const dim3 grid_pc(tgx + tiles_c + cgx * critics->n_nets + dl_on + xchg_on);
-        if (alate && tc == 16) SSAC_LAUNCH((fused_chain_pc_kernel<16, true, true>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        else if (alate) SSAC_LAUNCH((fused_chain_pc_kernel<32, true, true>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        else if (tc == 16 && adbuf) SSAC_LAUNCH((fused_chain_pc_kernel<16, true>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        else if (adbuf) SSAC_LAUNCH((fused_chain_pc_kernel<32, true>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        else if (tc == 16) SSAC_LAUNCH((fused_chain_pc_kernel<16, false>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        else SSAC_LAUNCH((fused_chain_pc_kernel<32, false>), grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        if (gather && gather->feed)
-            for (int a = 0; a < 3; ++a) ssac_record_slot_patch(a, offsetof(FusedArgs, slot_now));   // ga, gt, gc
+        SSAC_LAUNCH(pc_kernel, grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
+        if (gather && gather->feed) patch_slots(3);   // ga, gt, gc
         return ssac_check_launch("fused_chain_pc");
     }
     if (target_splits != 1) return ssac_fail("ssac_chain_update: column-split target critics need the hand-off form");
     if (xchg) return ssac_fail("ssac_chain_update: the in-launch exchange needs the hand-off (producer / consumer) form");
     const dim3 grid(tiles_t + cgx * critics->n_nets + dl_on);
-    if (tc == 16 && adbuf) SSAC_LAUNCH((fused_chain_kernel<16, true>), grid, dim3(NTHR), lds, st, ga, gr, gt, gc, tiles_t, tgx, cgx, dl, dl_on);
-    else if (adbuf) SSAC_LAUNCH((fused_chain_kernel<32, true>), grid, dim3(NTHR), lds, st, ga, gr, gt, gc, tiles_t, tgx, cgx, dl, dl_on);
-    else if (tc == 16) SSAC_LAUNCH((fused_chain_kernel<16, false>), grid, dim3(NTHR), lds, st, ga, gr, gt, gc, tiles_t, tgx, cgx, dl, dl_on);
-    else SSAC_LAUNCH((fused_chain_kernel<32, false>), grid, dim3(NTHR), lds, st, ga, gr, gt, gc, tiles_t, tgx, cgx, dl, dl_on);
-    if (gather && gather->feed)
-        for (int a = 0; a < 4; ++a) ssac_record_slot_patch(a, offsetof(FusedArgs, slot_now));   // ga, gr, gt, gc
+    SSAC_LAUNCH(chain_kernel, grid, dim3(NTHR), lds, st, ga, gr, gt, gc, tiles_t, tgx, cgx, dl, dl_on);
+    if (gather && gather->feed) patch_slots(4);   // ga, gr, gt, gc
     return ssac_check_launch("fused_chain");
 }
 
@@ -2303,9 +2307,7 @@ extern "C" int ssac_chain_target_splits(const ssac_mlp *actor, const ssac_mlp *t
                                         int n_sel) {
     if (!actor || !targets || !critics || n_rows <= 0 || n_sel <= 0) return 1;
     if (targets->hidden != 256 || targets->out_dim != 1 || actor->out_dim / 2 > 32) return 1;
-    FusedArgs gc{};
-    gc.n_rows = n_rows; gc.in_dim = critics->in_dim; gc.hidden = critics->hidden; gc.out_dim = critics->out_dim;
-    const int tc = choose_tile(gc, critics->n_nets).tm;
+    const int tc = choose_tile(critics, n_rows, critics->n_nets).tm;
     const int tgx = (n_rows + 15) / 16, cgx = (n_rows + tc - 1) / tc;
     for (int ns = 4; ns > 1; ns >>= 1)
         if (tgx + n_sel * ns * tgx + cgx * critics->n_nets + 1 <= 256) return ns;
@@ -2325,10 +2327,8 @@ extern "C" int ssac_critic_fwd_bwd_fused(const ssac_mlp *nets, const float *X, i
     FusedArgs g{};
     fill_common(g, nets, nullptr, X, ldx, 0, n_rows);
     g.H1 = H1; g.H2 = H2; g.Y = Q;
-    g.td = td; g.weight = weight; g.act = act; g.ld_a = ld_act; g.popart = popart; g.pop = pop;
-    g.denom = denom; g.DQ = DQ; g.DZ2 = DZ2; g.DZ1 = DZ1; g.partials = partials;
-    if (lazy_td) g.tds = *lazy_td;
-    if (!td && !lazy_td) return ssac_fail("ssac_critic_fwd_bwd_fused: no TD target given");
+    if (fill_loss("ssac_critic_fwd_bwd_fused", g, td, weight, act, ld_act, popart, pop, denom, DQ, DZ2, DZ1, partials, lazy_td))
+        return 1;
     return launch_fused<MODE_CRITIC>(g, nets->n_nets, (hipStream_t)stream);
 }
 
@@ -2344,10 +2344,8 @@ extern "C" int ssac_critic_bwd_fused(const ssac_mlp *nets, int n_rows, const flo
     FusedArgs g{};
     fill_common(g, nets, nullptr, nullptr, 0, 0, n_rows);
     g.H1 = const_cast<float *>(H1); g.H2 = const_cast<float *>(H2); g.Y = const_cast<float *>(Q);
-    g.td = td; g.weight = weight; g.act = act; g.ld_a = ld_act; g.popart = popart; g.pop = pop;
-    g.denom = denom; g.DQ = DQ; g.DZ2 = DZ2; g.DZ1 = DZ1; g.partials = partials;
-    if (lazy_td) g.tds = *lazy_td;
-    if (!td && !lazy_td) return ssac_fail("ssac_critic_bwd_fused: no TD target given");
+    if (fill_loss("ssac_critic_bwd_fused", g, td, weight, act, ld_act, popart, pop, denom, DQ, DZ2, DZ1, partials, lazy_td))
+        return 1;
     return launch_fused<MODE_CRITIC_BWD>(g, nets->n_nets, (hipStream_t)stream);
 }
 
@@ -2407,9 +2405,8 @@ extern "C" int ssac_actor_chain_fused(const ssac_mlp *actor, const float *X, int
     FusedArgs ga{}, gb{}, gc{};
     fill_common(ga, actor, nullptr, X, ldx, 0, n_rows);
     ga.H1 = H1; ga.H2 = H2; ga.Y = out;
-    ga.eps = eps; ga.lo = log_std_lo; ga.hi = log_std_hi;
-    if (rng) ga.rng = RngArgs{rng->seed, rng->counter, rng->offset};
-    ga.act_dst = xsa; ga.ld_act = ld_xsa; ga.act_col0 = S; ga.logp = logp; ga.copy_x = 1;
+    fill_sample(ga, eps, log_std_lo, log_std_hi, rng, xsa, ld_xsa, S, logp);
+    ga.copy_x = 1;
     ga.begin_logs = begin_logs; ga.begin_n = begin_logs ? n_logs : 0; ga.begin_ctl = begin_ctl;
     // the launch's tag: 1 + update_no (a caller-numbered update: every RECORDED launch is -- its replays are renumbered
     // through ssac_replay_value, which rewrites the tag and the noise draw in the recorded argument bytes), or a host counter
@@ -2435,25 +2432,12 @@ extern "C" int ssac_actor_chain_fused(const ssac_mlp *actor, const float *X, int
     // chip (one workgroup per CU at this LDS carve), or the critics they wait for could not start.  Half the CUs at most.
     if (tiles_a > SSAC_ACTOR_CHAIN_MAX_ROWS / 16)
         return ssac_fail("ssac_actor_chain_fused: more than SSAC_ACTOR_CHAIN_MAX_ROWS batch rows (use the three launches)");
-    size_t lds = fused_lds_bytes(actor->in_dim, actor->hidden, actor->out_dim, 16, adbuf);
-    const size_t lc = fused_lds_bytes(critics->in_dim, critics->hidden, critics->out_dim, tc, true);
-    if (lc > lds) lds = lc;
+    const size_t lds = max_lds(fused_lds_bytes(actor, 16, adbuf), fused_lds_bytes(critics, tc));
     if (lds > 160 * 1024) return ssac_fail("ssac_actor_chain_fused: LDS carve does not fit");
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *ks[4] = {(const void *)fused_actor_chain_kernel<16>, (const void *)fused_actor_chain_kernel<32>,
-                             (const void *)fused_actor_chain_kernel<16, false>, (const void *)fused_actor_chain_kernel<32, false>};
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return ssac_fail("fused_actor_chain: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    const auto kernel = ACTOR_CHAIN.pick(tc, adbuf ? FORM_DBUF : FORM_SINGLE);
+    if (!kernel) return 1;
     const dim3 grid(tiles_a + cgx * N);
-    hipStream_t st = (hipStream_t)stream;
-    if (tc == 16 && adbuf) SSAC_LAUNCH((fused_actor_chain_kernel<16>), grid, dim3(NTHR), lds, st, ga, gb, gc, tiles_a, cgx);
-    else if (adbuf) SSAC_LAUNCH((fused_actor_chain_kernel<32>), grid, dim3(NTHR), lds, st, ga, gb, gc, tiles_a, cgx);
-    else if (tc == 16) SSAC_LAUNCH((fused_actor_chain_kernel<16, false>), grid, dim3(NTHR), lds, st, ga, gb, gc, tiles_a, cgx);
-    else SSAC_LAUNCH((fused_actor_chain_kernel<32, false>), grid, dim3(NTHR), lds, st, ga, gb, gc, tiles_a, cgx);
+    SSAC_LAUNCH(kernel, grid, dim3(NTHR), lds, (hipStream_t)stream, ga, gb, gc, tiles_a, cgx);
     if (update_no >= 0) {   // (recorded: a replay's number replaces update_no in the tag and in the noise draw)
         for (int a = 0; a < 3; ++a) ssac_record_value_patch(a, offsetof(FusedArgs, ho) + offsetof(Handoff, base), 0, 1);
         if (rng && !rng->counter)
@@ -2470,9 +2454,7 @@ extern "C" int64_t ssac_actor_chain_handoff_words(int n_rows, int n_critics, int
 
 // row tiles the fused critic launch will use for (n_rows, n_nets): sizes the `partials` buffer
 extern "C" int ssac_fused_row_tiles(const ssac_mlp *nets, int n_rows, int n_nets) {
-    FusedArgs g{};
-    g.n_rows = n_rows; g.in_dim = nets->in_dim; g.hidden = nets->hidden; g.out_dim = nets->out_dim;
-    const int tm = choose_tile(g, n_nets).tm;
+    const int tm = choose_tile(nets, n_rows, n_nets).tm;
     return (n_rows + tm - 1) / tm;
 }
 
@@ -2517,8 +2499,7 @@ __global__ __launch_bounds__(64) void deferred_logs_kernel(DeferredLogsArgs d, i
 
 extern "C" int ssac_deferred_logs_flush(const ssac_deferred_logs *d, int ring_slot, void *stream) {
     if (!d || !d->feed || !d->partials || ring_slot < 0) return ssac_fail("ssac_deferred_logs_flush: bad arguments");
-    DeferredLogsArgs dl{d->partials, d->n_nets, d->sumsq, d->n_ss, d->td_stats, d->td_off, d->n_rows, d->denom, d->feed};
-    SSAC_LAUNCH(deferred_logs_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dl, ring_slot);
+    SSAC_LAUNCH(deferred_logs_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, deferred_args(d), ring_slot);
     return ssac_check_launch("deferred_logs");
 }
 

@@ -1240,15 +1240,10 @@ bool small_ok(const GemmArgs &g) {
 
 template <int EPI, int MB>
 int launch_pair_small(GemmPair &p, int batch, hipStream_t st) {
-    static bool attr_set = false;
+    static bool raised = false;
     const size_t lds = sizeof(float) * (S_PART + S_RED + (p.lf.q ? p.lf.n_rows + 2 * SW + 16 : 0));
     if (lds > 150 * 1024) return ssac_fail("wgrad_small_pair: the folded loss table does not fit LDS");
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void *)wgrad_small_pair_kernel<EPI, MB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024) != hipSuccess)
-            return ssac_fail("wgrad_small_pair: cannot raise the dynamic LDS limit");
-        attr_set = true;
-    }
+    if (ssac_raise_lds(raised, 150 * 1024, "wgrad_small_pair", wgrad_small_pair_kernel<EPI, MB>)) return 1;
     for (GemmArgs *g : {&p.g0, &p.g1}) {
         g->grid_x = (g->N + ST - 1) / ST;
         g->grid_y = (g->M + ST * MB - 1) / (ST * MB);
@@ -1270,7 +1265,7 @@ int launch_pair_small(GemmPair &p, int batch, hipStream_t st) {
 
 template <bool A_KC, bool B_KC, int EPI, int KS>
 int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
-    static bool attr_set = false;
+    static bool raised = false;
     const size_t lds = sizeof(float) * (KS * 4 * TILE_FLOATS + 64 * KS + (p.lf.q ? p.lf.n_rows + 16 * KS : 0));
     constexpr int PAIR_LDS_MAX = 160 * 1024 - 256;  // the kernel also has a few bytes of static LDS
     if (lds > PAIR_LDS_MAX) return ssac_fail("ens_gemm_pair: the folded loss table does not fit LDS");
@@ -1281,17 +1276,9 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
                (int64_t)(g.K + 1) * g.ldb < (1LL << 31);
     };
     const bool lean = TN_ && g_gemm_lean && vec_ok(p.g0) && vec_ok(p.g1);
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void *)ens_gemm_pair_kernel<A_KC, B_KC, EPI, KS>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_MAX) != hipSuccess)
-            return ssac_fail("ens_gemm_pair: cannot raise the dynamic LDS limit");
-        if constexpr (TN_) {
-            if (hipFuncSetAttribute((const void *)ens_gemm_pair_kernel<A_KC, B_KC, EPI, KS, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_LDS_MAX) != hipSuccess)
-                return ssac_fail("ens_gemm_pair: cannot raise the dynamic LDS limit");
-        }
-        attr_set = true;
-    }
+    const void *ks[2] = {(const void *)ens_gemm_pair_kernel<A_KC, B_KC, EPI, KS>, nullptr};
+    if constexpr (TN_) ks[1] = (const void *)ens_gemm_pair_kernel<A_KC, B_KC, EPI, KS, true>;
+    if (ssac_raise_lds(raised, ks, TN_ ? 2 : 1, PAIR_LDS_MAX, "ens_gemm_pair")) return 1;
     p.xcd = (g_ssac_xcd >> 1) & 1;
     p.tl = g_ssac_timeline;
     p.xcd_mix = 0;
@@ -1317,20 +1304,12 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
 
 template <bool A_KC, bool B_KC, int EPI, int KS>
 int launch_ks(const GemmArgs &g, dim3 grid, hipStream_t st) {
-    static bool attr_set = false;
+    static bool raised = false;
     const size_t lds = sizeof(float) * (KS * 4 * TILE_FLOATS + 64 * KS);
     constexpr bool TN_ = !A_KC && !B_KC;
-    if (!attr_set && lds > 48 * 1024) {
-        if (hipFuncSetAttribute((const void *)ens_gemm_kernel<A_KC, B_KC, EPI, KS>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return ssac_fail("ens_gemm: cannot raise the dynamic LDS limit");
-        if constexpr (TN_) {
-            if (hipFuncSetAttribute((const void *)ens_gemm_kernel<A_KC, B_KC, EPI, KS, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return ssac_fail("ens_gemm: cannot raise the dynamic LDS limit");
-        }
-        attr_set = true;
-    }
+    const void *ks[2] = {(const void *)ens_gemm_kernel<A_KC, B_KC, EPI, KS>, nullptr};
+    if constexpr (TN_) ks[1] = (const void *)ens_gemm_kernel<A_KC, B_KC, EPI, KS, true>;
+    if (lds > 48 * 1024 && ssac_raise_lds(raised, ks, TN_ ? 2 : 1, (int)lds, "ens_gemm")) return 1;
     if constexpr (TN_) {   // weight gradients: the lean kernel when the operands qualify (see launch_pair_ks)
         extern int g_gemm_lean;
         if (g_gemm_lean && (g.vec & 1) && (g.vec & 6) && g.Ktot <= 0 && g.K % BK == 0 &&

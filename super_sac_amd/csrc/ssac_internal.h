@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstring>
 #include <tuple>
 #include <vector>
@@ -86,6 +87,26 @@ inline void ssac_record_value_patch(int arg_index, size_t member_off, int kind, 
     if (!g_ssac_recording || g_ssac_recording->empty()) return;
     SsacLaunchRec &r = g_ssac_recording->back();
     r.value_patches.push_back(SsacLaunchRec::ValuePatch{r.offsets[(size_t)arg_index] + member_off, kind, addend, stride});
+}
+
+// Raise the dynamic-LDS limit of a GROUP of kernels (the instantiations one launcher chooses from), once: all of them on
+// the group's first launch.  `raised` is the group's flag -- a static beside the call, or of the table the launcher picks
+// its instantiation from.
+inline int ssac_raise_lds(bool &raised, const void *const *kernels, size_t n, int bytes, const char *name) {
+    if (raised) return 0;
+    for (size_t i = 0; i < n; ++i)
+        if (hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            char msg[128];
+            snprintf(msg, sizeof(msg), "%s: cannot raise the dynamic LDS limit", name);
+            return ssac_fail(msg);
+        }
+    raised = true;
+    return 0;
+}
+template <typename... K>
+inline int ssac_raise_lds(bool &raised, int bytes, const char *name, K... kernels) {
+    const void *ks[] = {(const void *)kernels...};
+    return ssac_raise_lds(raised, ks, sizeof...(K), bytes, name);
 }
 
 // ---------------------------------------------------------------------------------------------

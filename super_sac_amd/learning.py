@@ -31,9 +31,6 @@ def _critic_input(bt, ws, tag, s_rep, a, discrete):
     return x, x.stride(0)
 
 
-# Run the online critics' forward as a parallel branch beside the actor -> target critics -> TD-target chain.
-# Off by default: on MI355X a cross-stream join costs ~10 us of signalling (measured, also inside a HIP graph),
-# more than the overlap wins at the metric shape (6.6k vs 7.15k updates/s); tests exercise both settings.
 # how a repeated update is re-issued: "list" = the library's recorded launch list (ssac_replay), "graph" = a
 # hipGraph captured through torch.cuda.graph (leaves a ~13 us idle tail per launch on MI355X)
 LAUNCH_MODE = os.environ.get("SSAC_LAUNCH_MODE", "list")
@@ -83,6 +80,9 @@ FOLD_BEGIN = True  # fold ssac_begin_update into the replay gather
 # partials and publishes the log block; the separate 1-workgroup logs launch (~5 us per update) disappears.
 FOLD_LOGS = True
 LAZY_TD = True
+# Run the online critics' forward as a parallel branch beside the actor -> target critics -> TD-target chain.
+# Off by default: on MI355X a cross-stream join costs ~10 us of signalling (measured, also inside a HIP graph),
+# more than the overlap wins at the metric shape (6.6k vs 7.15k updates/s); tests exercise both settings.
 SPLIT_FORWARD = False
 
 
