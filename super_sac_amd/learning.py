@@ -8,7 +8,9 @@ hand-derived backward, and weight-gradient GEMMs whose epilogue is the Adam step
 logs stay on the device until somebody reads them.
 """
 import ctypes as C
+import operator
 import os
+import types
 
 import numpy as np
 import torch
@@ -17,18 +19,6 @@ from . import beta, engine, parallel, rng
 from . import learning_utils as lu
 from . import _lib
 from ._lib import check, lib
-
-
-def _critic_input(bt, ws, tag, s_rep, a, discrete):
-    """(X, ldx, in_dim) for the online critics: [s | a] (continuous) or s (discrete)."""
-    B, S = s_rep.shape
-    if bt is not None and bt.xsa is not None and s_rep.data_ptr() == bt.xsa.data_ptr():
-        return bt.xsa, bt.xsa.stride(0)
-    if discrete:
-        return s_rep, lu._row_stride(s_rep)
-    x = lu._concat_buffer(ws, tag, s_rep, a.shape[1])
-    x[:, S:].copy_(a)
-    return x, x.stride(0)
 
 
 # how a repeated update is re-issued: "list" = the library's recorded launch list (ssac_replay), "graph" = a
@@ -191,22 +181,13 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     observations, uniform sampling, single rank) it is captured once into a HIP graph and replayed:
     the host then only draws the indices / REDQ subset / noise, uploads them into fixed-address
     buffers and issues one graph launch, instead of ~15 kernel launches."""
+    kw = dict(locals())   # (first statement: exactly the arguments)
     # ---- fast path: this exact call has been recorded already (ssac_step: one C call re-issues the update)
     fast = agent.__dict__.get("_ssac_fast")
     if fast is not None and USE_GRAPHS and engine.CAPTURE is None:
-        fs = fast.get((id(buffer), id(target_agent), id(critic_optimizer), id(log_alphas[0]), id(augmenter), batch_size,
-                       gamma, critic_clip, encoder_clip, target_critic_ensemble_n, weighted_bellman_temp, weight_type,
-                       pop, encoder_lambda, id(random_process), noise_clip, discrete, per, update_priorities, dr3_coeff,
-                       engine.USE_FUSED))
+        fs = fast.get(_fast_key(kw))
         if fs is not None and fs.still_valid():
             return fs.run()
-    kw = dict(buffer=buffer, agent=agent, target_agent=target_agent, critic_optimizer=critic_optimizer,
-              encoder_optimizer=encoder_optimizer, log_alphas=log_alphas, batch_size=batch_size, gamma=gamma,
-              critic_clip=critic_clip, encoder_clip=encoder_clip,
-              target_critic_ensemble_n=target_critic_ensemble_n, weighted_bellman_temp=weighted_bellman_temp,
-              weight_type=weight_type, pop=pop, augmenter=augmenter, encoder_lambda=encoder_lambda,
-              random_process=random_process, noise_clip=noise_clip, aug_mix=aug_mix, discrete=discrete, per=per,
-              update_priorities=update_priorities, dr3_coeff=dr3_coeff)
     lu.ensure_adopted(agent, buffer)
     lu.ensure_adopted(target_agent, buffer)
     shard = parallel.shard_of(agent)
@@ -238,12 +219,31 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     if (gs.graph is not None and LAUNCH_MODE == "list" and getattr(gs, "fast", None) is None
             and all(not callable(p_) for p_ in gs.graph.parts)):
         gs.fast = _FastStep(gs, kw)
-        agent.__dict__.setdefault("_ssac_fast", {})[
-            (id(buffer), id(target_agent), id(critic_optimizer), id(log_alphas[0]), id(augmenter), batch_size,
-             gamma, critic_clip, encoder_clip, target_critic_ensemble_n, weighted_bellman_temp, weight_type,
-             pop, encoder_lambda, id(random_process), noise_clip, discrete, per, update_priorities, dr3_coeff,
-             engine.USE_FUSED)] = gs.fast
+        agent.__dict__.setdefault("_ssac_fast", {})[_fast_key(kw)] = gs.fast
     return out
+
+
+_fast_values = operator.itemgetter("batch_size", "gamma", "critic_clip", "encoder_clip", "target_critic_ensemble_n",
+                                   "weighted_bellman_temp", "weight_type", "pop", "encoder_lambda", "noise_clip", "discrete",
+                                   "per", "update_priorities", "dr3_coeff")
+
+
+def _fast_key(kw):   # what identifies a recorded call critic_update(**kw) among its agent's recordings
+    return (id(kw["buffer"]), id(kw["target_agent"]), id(kw["critic_optimizer"]), id(kw["log_alphas"][0]),
+            id(kw["augmenter"]), id(kw["random_process"]), engine.USE_FUSED) + _fast_values(kw)
+
+
+def _slot_codes(row, ids, shard):
+    # sharded: the LOCAL index of a subset member this rank owns, -(owner rank + 1) for one that lives elsewhere
+    for j, v in enumerate(ids):
+        row[j] = v if shard is None else shard.slot_code(v)
+
+
+def _recorded_result(gs, idx_cpu, ids, logs):
+    rd = gs.dicts[0]
+    rd["priority_idxs"] = idx_cpu.numpy()
+    rd["_subset"] = ids
+    return logs, gs.dicts
 
 
 def _flush_other_recordings(agent, keep=None):
@@ -332,9 +332,7 @@ class _FastStep:
             rng.draw_normal_into(gs.eps_dev)  # injected noise (parity tests)
         ids = rng.draw_subset(self.n_critics, self.n_sub)
         ida, sh = self.ids_c, self.shard
-        for j, v in enumerate(ids):
-            # sharded: the LOCAL index of a subset member this rank owns, -(owner rank + 1) for one that lives elsewhere
-            ida[j] = v if sh is None else sh.slot_code(v)
+        _slot_codes(ida, ids, sh)
         slot_i = self.ring.advance()
         if sh is not None and gs.k % EVENT_EVERY == 0:
             parallel.check_exchange()
@@ -350,11 +348,7 @@ class _FastStep:
         if gs.deferred is not None:
             gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
         rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
-        logs = gs.views(self.ring, slot_i)
-        rd = gs.dicts[0]
-        rd["priority_idxs"] = idx_cpu.numpy()
-        rd["_subset"] = ids
-        return dict(logs), gs.dicts
+        return _recorded_result(gs, idx_cpu, ids, dict(gs.views(self.ring, slot_i)))
 
     def __del__(self):
         try:
@@ -449,9 +443,7 @@ def _critic_update_graphed(gs, kw):
     slot_i = ring.advance()
     gs.np_idx[k] = idx_cpu.numpy()
     row = gs.np_i32[k]
-    for j, v in enumerate(ids):
-        # sharded: the LOCAL index of a subset member this rank owns, -(owner rank + 1) for one that lives elsewhere
-        row[j] = v if shard is None else shard.slot_code(v)
+    _slot_codes(row, ids, shard)
     row[gs.n_pad] = slot_i
     if in_kernel_noise:
         gs.np_draw[k, 0] = lu.noise_stream(agent, dev)[1]
@@ -472,9 +464,8 @@ def _critic_update_graphed(gs, kw):
         ctx.defer_begin = (FOLD_BEGIN and agent.ensemble_size == 1 and len(keys_) == 1
                            and st_.s_stack[keys_[0]].dim() == 2)
         c_arena_ = agent.critics[0].arena(dev)
-        if (lu.DEFERRED_LOGS and LAUNCH_MODE == "list" and FOLD_LOGS and FOLD_LOSS and LAZY_TD and ctx.defer_begin
-                and not kw["critic_clip"] and kind == "stochastic" and not any(agent.popart) and c_arena_.out_dim == 1
-                and B <= 4096):
+        if (lu.DEFERRED_LOGS and LAUNCH_MODE == "list" and FOLD_LOGS and _loss_folds(B) and LAZY_TD and ctx.defer_begin
+                and not kw["critic_clip"] and kind == "stochastic" and not any(agent.popart) and c_arena_.out_dim == 1):
             # deferred log finalisation (csrc/ssac_critic_logs.h): the buffers the weight-gradient launch will leave
             # its partials in are workspace tensors with fixed names, so the struct can be built before the body runs
             ws_ = lu.agent_ws(agent, dev)
@@ -493,8 +484,10 @@ def _critic_update_graphed(gs, kw):
                 ctx.late = gs.late_word.data_ptr()
                 ctx.late_target = t_arena_
 
+        gs.members = []   # the members' records: what a replay reads lives as long as the recording
+
         def body():
-            logs_, dicts_ = _critic_update_eager(**kw)
+            logs_, dicts_ = _critic_update_eager(_records=gs.members, **kw)
             assert not ctx.pending_begin, "deferred ssac_begin_update was never issued"
             assert ctx.deferred_used == ctx.deferred_chain, "deferred log finalisation: chain / weight-gradient mismatch"
             gs.deferred = ctx.deferred if ctx.deferred_used else None
@@ -547,58 +540,58 @@ def _critic_update_graphed(gs, kw):
     rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
     if gs.deferred is not None:
         gs.pending = slot_i
-    logs = dict(gs.views(ring, slot_i))
-    rd = gs.dicts[0]
-    rd["priority_idxs"] = idx_cpu.numpy()
-    rd["_subset"] = ids
-    return logs, gs.dicts
+    return _recorded_result(gs, idx_cpu, ids, dict(gs.views(ring, slot_i)))
 
 
-def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_optimizer, log_alphas,
-                         batch_size, gamma, critic_clip, encoder_clip, target_critic_ensemble_n,
-                         weighted_bellman_temp, weight_type, pop, augmenter, encoder_lambda, random_process,
-                         noise_clip, aug_mix=0.75, discrete=False, per=False, update_priorities=False,
-                         dr3_coeff=0.0):
+def _loss_folds(n_rows):
+    """may the weight-gradient launch that follows a rank-1 backward evaluate dL/dq itself (the loss-fold form)?"""
+    return FOLD_LOSS and n_rows <= 4096   # the library's limit (include/ssac_hip.h, ssac_mlp_wgrad_all_lossfold: "n_rows <= 4096")
+
+
+def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_optimizer, log_alphas, batch_size, gamma,
+                         critic_clip, encoder_clip, target_critic_ensemble_n, weighted_bellman_temp, weight_type, pop,
+                         augmenter, encoder_lambda, random_process, noise_clip, aug_mix=0.75, discrete=False, per=False,
+                         update_priorities=False, dr3_coeff=0.0, _records=None):
+    """the ensemble-level flow; _records (a list, the recording's) receives the members' MemberUpdate records"""
+    c = types.SimpleNamespace(**locals())   # the call: its arguments, and below what every member shares
     engine.require_gpu()
     if engine.CAPTURE is None:
         agent.critics[0].__dict__.pop("_ssac_last_step", None)
         _flush_other_recordings(agent)
-    E = agent.ensemble_size
+    E = c.E = agent.ensemble_size
     assert E <= lu.MAX_MEMBERS
     # member-sharded rank (parallel.MemberShard, SURVEY 8(e) "SUNRISE variant"): `agent` holds the members [ms.lo, ms.hi)
     # of an ensemble of E_glob; the loss is averaged over the GLOBAL ensemble, every member's host draws are made here
-    ms = parallel.member_shard_of(agent)
-    E_glob = E if ms is None else ms.ensemble_size
+    ms = c.ms = parallel.member_shard_of(agent)
+    E_glob = c.E_glob = E if ms is None else ms.ensemble_size
     if ms is not None:
         assert lu.is_identity(agent.encoder), "member sharding: a trainable encoder is shared by all members (not sharded)"
         assert not per and not update_priorities and not dr3_coeff, "member sharding covers the online critic update"
         assert weight_type in (None, "sunrise", "softmax"), f"unknown weight_type {weight_type!r}"
-    dev = log_alphas[0].device
-    ws = lu.agent_ws(agent, dev)
-    adam = engine.adam_group(critic_optimizer, dev)
-    slot = lu.log_block(dev, adam)  # one launch: clear the log block + advance the Adam step
-    logs = {}
-    st = engine.stream()
-    clip_members = []
-    replay_dicts = []
-    member_ss = []
-    fused_logs = []
-    logs_done_in_wgrad = False
+    dev = c.dev = log_alphas[0].device
+    ws = c.ws = lu.agent_ws(agent, dev)
+    adam = c.adam = engine.adam_group(critic_optimizer, dev)
+    slot = c.slot = lu.log_block(dev, adam)  # one launch: clear the log block + advance the Adam step
+    logs = c.logs = {}
+    st = c.st = engine.stream()
+    c.train_enc = not lu.is_identity(agent.encoder)
     # Two passes over the ensemble members, as the reference's single backward at the end implies (learning.py:45-130):
     # every member's batch, TD target and backup weights are computed BEFORE any critic is updated -- the "softmax"
     # weights of member i look at the ONLINE critics of ALL members (learning_utils.py:383-393).
-    preps = []
-    all_rd = []   # member-sharded ranks: every global member's batch, in member order
+    members = [] if _records is None else _records
+    all_rd = c.all_rd = []   # member-sharded ranks: every global member's batch, in member order
     # member-sharded "softmax" weights (round 5): every member's policy samples on EVERY member's batch, drawn in the
     # reference's order -- right behind that batch's TD draws -- by every rank; the table is completed after the loop
     ms_softmax = (ms is not None and weight_type == "softmax" and weighted_bellman_temp is not None and E_glob > 1)
-    sm_table = None
+    sm_table = c.sm_table = ws.get("bw.table", (E_glob, E_glob, batch_size)) if ms_softmax else None
     if ms_softmax:
-        sm_table = ws.get("bw.table", (E_glob, E_glob, batch_size))   # [batch of member i][member k][row]
-        sm_table.zero_()
+        sm_table.zero_()   # [batch of member i][member k][row]
     for ig in range(E_glob):
         i = ig if ms is None else ms.local(ig)
-        if i is None:
+        if i is not None:
+            members.append(lu.MemberUpdate(i, ig, agent.critics[i].arena(dev)))
+            _member_targets(members[-1], c)
+        else:
             # a member another rank owns: its batch (this rank's target critics score it for the sunrise weights) and
             # its host draws, in the reference's order -- sample, action noise, REDQ subset
             rd = lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter,
@@ -608,302 +601,18 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
             if ms_softmax:
                 lu.member_sharded_softmax_scores(rd, agent, target_agent, ms, sm_table[ig])
             all_rd.append(rd)
-            continue
-        arena = agent.critics[i].arena(dev)
-        N, qd = arena.n_nets, arena.out_dim
-        H = arena.hidden
-        tag = f"cu.c{i}"
-        train_enc = not lu.is_identity(agent.encoder)
-        # when the merged actor / critic-forward launch will run, its workgroups fetch their own replay rows
-        # (ssac_gather) and the update has no gather launch
-        dual_ok = (DUAL_LAUNCH and arena.fused_dbuf and not train_enc and not dr3_coeff and not discrete
-                   and _dual_fits(arena, batch_size) and not _split_forward(N, batch_size))
-        rd = lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter,
-                                        aug_mix=aug_mix, per=per, _defer_gather=dual_ok,
-                                        _invariance=bool(encoder_lambda))
-        o, a, r, o1, d = rd["primary_batch"]
-        B = r.shape[0]
-        # The online critics' FORWARD does not depend on the TD target: on a second stream (a parallel graph
-        # branch) it overlaps the actor -> target critics -> TD-target chain, which occupies few CUs.
-        branch = None
-        if arena.fused and not train_enc and not dr3_coeff and _split_forward(N, B):
-            s_rep = lu.encode(agent.encoder, o)
-            X, ldx = _critic_input(rd.get("_ssac"), ws, f"cu.x{i}", s_rep, a, discrete)
-            with engine.side_stream(dev, defer_join=True) as branch:
-                with engine._timed("critic_fwd"):
-                    h1, h2, q = engine.mlp_forward(arena, X, ldx, 0, B, ws, tag)
-        co = cob = None
-        if dual_ok and branch is None:
-            # the critics' forward rides in the actor's launch (when compute_td_targets uses the fused sample
-            # launch); the critic launch below is then only the backward half
-            s_rep = lu.encode(agent.encoder, o)
-            X, ldx = _critic_input(rd.get("_ssac"), ws, f"cu.x{i}", s_rep, a, discrete)
-            co = (arena, X, ldx, ws.get(tag + ".h1", (N, B, H)), ws.get(tag + ".h2", (N, B, H)),
-                  ws.get(tag + ".y", (N, B, qd)))
-            if RANK1_BWD and qd == 1:
-                # and the TD-independent half (rank-1 loss gradient) of the backward pass rides in the target critics' launch
-                cob = (arena, co[3], co[4], a, a.stride(0), ws.get(tag + ".dz2", (N, B, H)),
-                       ws.get(tag + ".dz1", (N, B, H)))
-                # dz2u = W3 (.) [h2 > 0] need not leave the chained launch when the weight-gradient launch that follows
-                # is the loss-fold form: its fc2 tiles rebuild it from the saved h2 while staging (same values, bit for
-                # bit; 5 MB less written per update at the metric shape).  The chain launch reports whether it skipped.
-                rd["_dz2_optional"] = (SKIP_DZ2 and FOLD_LOSS and B <= 4096 and arena.shadow is None
-                                       and parallel.shard_of(agent) is None
-                                       and H % 4 == 0)
-        td, _ = lu.compute_td_targets(logs=logs, replay_dict=rd, agent=agent, target_agent=target_agent,
-                                      ensemble_idx=i, ensemble_n=target_critic_ensemble_n,
-                                      log_alphas=log_alphas, pop=pop, gamma=gamma,
-                                      random_process=random_process, noise_clip=noise_clip,
-                                      discrete=discrete, _slot=slot, _defer=arena.fused and LAZY_TD and not dr3_coeff,
-                                      _co_forward=co, _co_backward=cob, _log_idx=ig)
-        lu.ensure_gathered(rd.get("_ssac"))  # (no-op when the merged launch took the gather)
-        co_done = bool(rd.pop("_co_fwd", False))
-        bwd_done = bool(rd.pop("_co_bwd", False))
-        if co_done:
-            h1, h2, q = co[3], co[4], co[5]
-        all_rd.append(rd)
-        if ms_softmax:
-            lu.member_sharded_softmax_scores(rd, agent, target_agent, ms, sm_table[ig])
-        bw = 1.0 if ms is not None else \
-            lu.compute_backup_weights(logs=logs, replay_dict=rd, agent=agent, target_agent=target_agent,
-                                      weight_type=weight_type, weight_temp=weighted_bellman_temp,
-                                      batch_size=batch_size, discrete=discrete, _slot=slot)
-        preps.append(dict(arena=arena, rd=rd, branch=branch, co=co, td=td, co_done=co_done, bwd_done=bwd_done, bw=bw,
-                          fwd=(h1, h2, q) if (co_done or branch is not None) else None,
-                          xin=(s_rep, X, ldx) if (branch is not None or co is not None) else None))
     if ms is not None and weight_type is not None and weighted_bellman_temp is not None and E_glob > 1:
         if ms_softmax:
             wts = lu.member_sharded_softmax_finish(logs, sm_table, ms, weighted_bellman_temp, slot)
         else:
             wts = lu.member_sharded_sunrise_weights(logs, all_rd, agent, target_agent, ms, weighted_bellman_temp, discrete, slot)
-        for i, P in enumerate(preps):
-            P["bw"] = wts[ms.lo + i]
-    for i, P in enumerate(preps):
-        arena, rd, branch, co, td, co_done, bwd_done, bw = (P[k_] for k_ in ("arena", "rd", "branch", "co", "td",
-                                                                             "co_done", "bwd_done", "bw"))
-        N, qd, H = arena.n_nets, arena.out_dim, arena.hidden
-        tag = f"cu.c{i}"
-        train_enc = not lu.is_identity(agent.encoder)
-        o, a, r, o1, d = rd["primary_batch"]
-        B = r.shape[0]
-        if P["fwd"] is not None:
-            h1, h2, q = P["fwd"]
-        if P["xin"] is not None:
-            s_rep, X, ldx = P["xin"]
-        if train_enc:
-            # online encoder WITH gradient (learning.py:83): embedding goes straight into the critic input
-            xin = ws.get(f"cu.x{i}", (B, arena.in_dim))
-            inv = None
-            okey = getattr(agent.encoder, "ssac_obs_key", "obs")
-            # (the invariance constraint looks at the LAST member's batch only: learning.py:114-117 read the replay
-            # dict the member loop left behind)
-            lam_i = encoder_lambda if i == E - 1 else 0
-            if lam_i and rd["augmented_obs"][0][okey] is not o[okey]:
-                # encoder invariance on a partly augmented batch: the fully augmented observations need an encoder
-                # pass of their own WITH gradient -- one stacked 2B-row pass [o ; ao], whose backward then receives
-                # the critics' gradient in rows [0, B) and the constraint's in rows [B, 2B)
-                from . import conv_encoder
-                eng = conv_encoder.conv_engine(agent.encoder, dev)
-                img2 = ws.get("cu.img2", (2 * B,) + tuple(o[okey].shape[1:]))
-                img2[:B].copy_(o[okey])
-                img2[B:].copy_(rd["augmented_obs"][0][okey])
-                sall = ws.get("cu.sall", (2 * B, eng.emb))
-                eng.forward(img2, sall, eng.emb, True)
-                xin[:, :eng.emb].copy_(sall[:B])
-                s_rep, as_rep, stacked = xin[:, :eng.emb], sall[B:], True
-            else:
-                s_rep = lu.encode(agent.encoder, o, dst=xin, save=True)
-                as_rep, stacked = s_rep, False
-            if lam_i:
-                oo = rd["original_obs"][0]
-                if oo[okey] is o[okey]:
-                    os_rep = ws.get("cu.osrep", (B, s_rep.shape[1]))
-                    os_rep.copy_(s_rep)   # un-augmented batch: the target of the constraint is the embedding itself
-                else:
-                    os_rep = lu.encode(agent.encoder, oo, dst=ws.get("cu.osrep", (B, s_rep.shape[1])), save=False)
-                inv = (as_rep, os_rep, encoder_lambda, stacked)
-                logs["encoder_constraint_loss"] = slot[lu.L_ENC_INV]
-            if not discrete:
-                xin[:, s_rep.shape[1]:].copy_(a)
-            X, ldx = xin, xin.stride(0)
-        elif branch is None and co is None:
-            s_rep = lu.encode(agent.encoder, o)
-            X, ldx = _critic_input(rd.get("_ssac"), ws, f"cu.x{i}", s_rep, a, discrete)
-        if encoder_lambda and not train_enc:
-            # identity encoder: augmented == original observations (only the identity augmentation applies to vectors),
-            # the constraint is exactly zero and has no parameter to reach (learning_utils.py:401-409)
-            logs["encoder_constraint_loss"] = slot[lu.L_ENC_INV]
-        shard = parallel.shard_of(agent)
-        n_glob = N if shard is None else shard.num_critics  # loss is averaged over the GLOBAL ensemble
-        popart = agent.popart[i]
-        weight_ptr = 0
-        if not isinstance(bw, float):
-            weight_ptr = bw.data_ptr()  # imp_weights is ones(1) on the uniform path
-        if per:
-            # learning.py:96-98 multiplies (B,1) errors by the (B,) importance weights: a (B,B) outer product
-            # whose mean is mean(w) * mean(bw * err^2) -- i.e. every row's weight is scaled by mean(w)
-            wrow = ws.get(f"cu.w{i}", (B, 1))
-            scale = rd["imp_weights"].mean().to(torch.float32)
-            if isinstance(bw, float):
-                wrow.fill_(1.0)
-            else:
-                wrow.copy_(bw.view(B, 1))
-            wrow.mul_(scale)
-            weight_ptr = wrow.data_ptr()
-        pp, dopop = (popart.ptr if popart else 0), (1 if (popart and pop) else 0)
-        ttot = engine.bf16_tiles_total(arena) if arena.shadow is not None else engine.wgrad_tiles_total(arena)
-        ss = ws.get(f"cu.ss{i}", (N * ttot,))
-        dq = ws.get(f"cu.dq{i}", (N, B, qd))
-        grads = ws.get(f"cu.g{i}", (arena.params.numel(),), zero=True) if critic_clip else None
-        if dr3_coeff:
-            # DR3 (learning.py:100-108): the critics also run on (s', a'); both batches go through the per-layer
-            # kernels as ONE stacked 2B-row batch, the co-adaptation gradient enters at the fc2 pre-activations
-            assert not train_enc and shard is None, "DR3 is supported for identity encoders on a single rank"
-            x1 = rd.get("_x1")
-            X1 = x1 if x1 is not None else lu.encode(target_agent.encoder, o1)
-            Xc = ws.get(f"cu.xcat{i}", (2 * B, arena.in_dim))
-            Xc[:B].copy_(torch.as_strided(X, (B, arena.in_dim), (ldx, 1)))
-            Xc[B:].copy_(X1[:, :arena.in_dim])
-            ch1, ch2, cq = engine.mlp_forward(arena, Xc, arena.in_dim, 0, 2 * B, ws, tag + ".dr3", force_layers=True)
-            qc = ws.get(tag + ".dr3.qc", (N, B, qd))
-            qc.copy_(cq[:, :B])
-            dqc = ws.get(tag + ".dr3.dqc", (N, B, qd))
-            check(lib.ssac_critic_loss_bwd(qc.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), td.data_ptr(),
-                                           weight_ptr, pp, dopop, float(E_glob * n_glob), dqc.data_ptr(),
-                                           slot.data_ptr(), st))
-            dq2 = ws.get(tag + ".dr3.dq", (N, 2 * B, qd), zero=True)
-            dq2[:, :B].copy_(dqc)
-            nblk = int(lib.ssac_dr3_blocks())
-            dparts = ws.get(tag + ".dr3.parts", (nblk,))
-            coef = float(dr3_coeff) / (E_glob * n_glob) / (N * B)
-
-            def dr3_hook(dz2_, _h2=ch2, _parts=dparts):
-                check(lib.ssac_dr3_add(dz2_.data_ptr(), _h2.data_ptr(), N, B, H, coef, _parts.data_ptr(), st))
-            engine.mlp_backward(arena, dq2, Xc, arena.in_dim, 0, ch1, ch2, 2 * B, ws, tag + ".dr3", adam=adam,
-                                adam_key=("critic", i), grads=grads, sumsq=ss, after_dz2=dr3_hook)
-            fca = dparts.sum() / (N * B)
-            logs[f"dr3_dotproduct_{i}"] = fca
-            # the logged overall loss includes the regulariser (learning.py:108, 133)
-            slot[lu.L_CRITIC_LOSS:lu.L_CRITIC_LOSS + 1].add_(fca * (float(dr3_coeff) / (E_glob * n_glob)))
-            fused_logs.append(None)
-        elif arena.fused:
-            dz2 = ws.get(tag + ".dz2", (N, B, H))
-            dz1 = ws.get(tag + ".dz1", (N, B, H))
-            tiles = int(lib.ssac_fused_row_tiles(C.byref(arena.desc()), B, N))
-            parts = ws.get(tag + ".parts", (N * tiles * 2,))
-            spec = getattr(td, "_ssac_spec", None)  # the TD target is evaluated inside the critic launch
-            spec_ptr = C.addressof(spec) if spec is not None else 0
-            lossfold = None
-            w3_snapshot = rd.pop("_dz2_skipped", None)
-            dz2_skipped = w3_snapshot is not None
-            if dz2_skipped and not (bwd_done and FOLD_LOSS and B <= 4096):
-                raise RuntimeError("internal: the chained launch skipped dz2u but no loss-fold weight-gradient launch follows")
-            if bwd_done and FOLD_LOSS and B <= 4096:
-                # dz2u / dz1u exist already; what depends on the TD target is one scalar per (net, row), dL/dq, and the
-                # weight-gradient launch evaluates it itself (per workgroup, in LDS): no loss launch at all
-                fparts = ws.get(tag + ".fparts", (N * 2,))
-                lossfold = dict(q=q, td_ptr=0 if spec is not None else td.data_ptr(), spec_ptr=spec_ptr,
-                                weight_ptr=weight_ptr, popart_ptr=pp, pop=dopop, denom=float(E_glob * n_glob),
-                                partials=fparts, dz2_from_h2=dz2_skipped, w3_snapshot=w3_snapshot)
-                if arena.shadow is not None:
-                    lossfold["bf"] = arena.bf_buffers(ws, "cu", B)
-                cap = engine.CAPTURE
-                if cap is not None and cap.deferred is not None and cap.deferred_chain and spec is not None:
-                    cap.deferred_used = True
-                    # recorded update: the launch leaves partials + TD statistics behind and advances the input ring;
-                    # the next update's first launch (or a flush) writes the ring slot
-                    late_ptr = 0
-                    if cap.late is not None:
-                        late_ptr = cap.late
-                        cap.late_used = True
-                        lossfold["late_target"] = cap.late_target.params
-                        if arena.shadow is not None:
-                            lossfold["target_shadow"] = cap.late_target.shadow
-                    lossfold["logfold"] = _lib.LogFold(0, slot.data_ptr(), 0, cap.feed, cap.deferred.td_stats, late_ptr)
-                elif FOLD_LOGS and E_glob == 1 and not critic_clip:
-                    # the log finalisation rides in the weight-gradient launch (its last workgroup to arrive): no logs launch
-                    lossfold["logfold"] = _lib.LogFold(
-                        ws.get("cu.done", (1,), dtype=torch.int32, zero=True).data_ptr(), slot.data_ptr(),
-                        td._ssac_logs.data_ptr() if spec is not None else 0,
-                        cap.feed if (cap is not None and cap.feed) else 0, 0, 0)
-            elif bwd_done:
-                # ... or a single-workgroup launch writes the N x B scalars for the weight-gradient launch to read
-                if spec is not None:
-                    check(lib.ssac_critic_loss_bwd_lazy(q.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), spec_ptr,
-                                                        weight_ptr, pp, dopop, float(E_glob * n_glob), dq.data_ptr(),
-                                                        slot.data_ptr(), st))
-                else:
-                    check(lib.ssac_critic_loss_bwd(q.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), td.data_ptr(),
-                                                   weight_ptr, pp, dopop, float(E_glob * n_glob), dq.data_ptr(),
-                                                   slot.data_ptr(), st))
-            elif branch is not None or co_done:
-                # loss gradient + head backward + backward-data on the saved forward: ONE launch
-                if branch is not None:
-                    branch.join()
-                with engine._timed("critic_bwd") as tm:
-                    for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
-                        check(lib.ssac_critic_bwd_fused(
-                            C.byref(arena.desc()), B, td.data_ptr(), weight_ptr, a.data_ptr(), a.stride(0), pp,
-                            dopop, float(E_glob * n_glob), h1.data_ptr(), h2.data_ptr(), q.data_ptr(), dq.data_ptr(),
-                            dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), spec_ptr, st))
-            else:
-                # forward of all N critics + loss gradient + backward-data: ONE launch
-                h1 = ws.get(tag + ".h1", (N, B, H))
-                h2 = ws.get(tag + ".h2", (N, B, H))
-                q = ws.get(tag + ".y", (N, B, qd))
-                with engine._timed("critic_fused") as tm:
-                    for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
-                        check(lib.ssac_critic_fwd_bwd_fused(
-                            C.byref(arena.desc()), X.data_ptr(), ldx, B, td.data_ptr(), weight_ptr, a.data_ptr(),
-                            a.stride(0), pp, dopop, float(E_glob * n_glob), h1.data_ptr(), h2.data_ptr(), q.data_ptr(),
-                            dq.data_ptr(), dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), spec_ptr, st))
-            if train_enc:  # dL/d(embedding) = sum over critics of dz1 W1[:, :emb], BEFORE W1 is updated
-                dX = ws.get(tag + ".dx", (N, B, arena.in_dim))
-                check(lib.ssac_mlp_layer_dgrad(C.byref(arena.desc()), 0, 0, N, dz1.data_ptr(), H, B * H, 0, 0, 0,
-                                               B, dX.data_ptr(), arena.in_dim, B * arena.in_dim, st))
-                _encoder_step(agent.encoder, encoder_optimizer, encoder_clip, dX, s_rep.shape[1], ws, slot, dev, inv,
-                              accumulate=i > 0, step=i == E - 1)
-            if arena.shadow is not None and lossfold is None:
-                raise NotImplementedError(
-                    "bf16 mode covers the chained critic update (continuous single-output critics, stochastic actor, "
-                    "identity encoder, with or without PopArt / gradient clipping; no DR3, no discrete critics)")
-            folded = engine.weight_grads(arena, X, ldx, 0, h1, h2, dq, dz2, dz1, B, adam=adam,
-                                         adam_key=("critic", i), grads=grads, sumsq=ss,
-                                         rowscale=dq if (bwd_done and lossfold is None) else None, lossfold=lossfold,
-                                         target=lossfold.get("late_target") if lossfold is not None else None)
-            if folded:
-                logs_done_in_wgrad = True
-                if lossfold["logfold"].feed:
-                    engine.CAPTURE.published = True
-            if lossfold is not None:
-                fused_logs.append((lossfold["partials"], N, 1, B, n_glob, td))
-            else:
-                fused_logs.append((parts, 0 if bwd_done else N, tiles, B, n_glob, td))
-        else:
-            if arena.shadow is not None:
-                raise NotImplementedError("bf16 mode needs the fused kernel family (hidden % 32 == 0, <= 256)")
-            h1, h2, q = engine.mlp_forward(arena, X, ldx, 0, B, ws, tag)
-            check(lib.ssac_critic_loss_bwd(q.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0),
-                                           td.data_ptr(), weight_ptr, pp, dopop, float(E_glob * n_glob),
-                                           dq.data_ptr(), slot.data_ptr(), st))
-            if train_enc:
-                dX = engine.mlp_backward(arena, dq, X, ldx, 0, h1, h2, B, ws, tag, need_dx=True, update=False)
-                _encoder_step(agent.encoder, encoder_optimizer, encoder_clip, dX, s_rep.shape[1], ws, slot, dev, inv,
-                              accumulate=i > 0, step=i == E - 1)
-                dz2, dz1 = ws.get(tag + ".dz2", (N, B, arena.hidden)), ws.get(tag + ".dz1", (N, B, arena.hidden))
-                engine.weight_grads(arena, X, ldx, 0, h1, h2, dq, dz2, dz1, B, adam=adam,
-                                    adam_key=("critic", i), grads=grads, sumsq=ss)
-            else:
-                engine.mlp_backward(arena, dq, X, ldx, 0, h1, h2, B, ws, tag, adam=adam,
-                                    adam_key=("critic", i), grads=grads, sumsq=ss)
-            fused_logs.append(None)
-        if critic_clip:
-            clip_members.append((arena, ("critic", i), grads, ss))
-        member_ss.append(ss)
-        rd["td_target"] = td
-        replay_dicts.append(rd)
+        for m in members:
+            m.bw = wts[ms.lo + m.i]
+    for m in members:
+        _member_step(m, c)
+        m.rd["td_target"] = m.td
     if critic_clip:
-        _clip_and_step(adam, clip_members, critic_clip, None, member_shard=ms)
+        _clip_and_step(adam, [(m.arena, ("critic", m.i), m.grads, m.ss) for m in members], critic_clip, None, ms)
     # encoder: identity encoders carry no trainable tensor on this path (their dummy Linear(1,1)
     # never receives a gradient, nets/__init__.py:24), so encoder_optimizer.step() is a no-op.
     logs["losses/last_member_critic_td_error"] = slot[lu.L_TD_ERR]
@@ -914,34 +623,308 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
         k = ms.local(rng.choice(range(E_glob))) or 0
     else:
         pick = agent.critics[0] if engine.CAPTURE is not None else rng.choice(agent.critics)  # learning.py:135
-        k = next(j for j, c in enumerate(agent.critics) if c is pick)
+        k = next(j for j, c_ in enumerate(agent.critics) if c_ is pick)
+    ss_k = members[k].ss
     clip_ctl = adam.ctl.ptr if critic_clip else 0
-    done_norm = False
-    for j, fl in enumerate(fused_logs):
-        if fl is None or logs_done_in_wgrad:
-            done_norm = done_norm or logs_done_in_wgrad
+    done_norm = logs_done_in_wgrad = any(m.logs_folded for m in members)
+    for m in members:
+        if m.log_parts is None or logs_done_in_wgrad:
             continue
-        parts, n_, tiles_, b_, ng_, td_ = fl
-        spec_ = getattr(td_, "_ssac_spec", None)
-        want = j == k
+        want = m.i == k
         cap = engine.CAPTURE
-        last = cap is not None and cap.feed and j == len(fused_logs) - 1 and (done_norm or want)
-        check(lib.ssac_critic_logs(parts.data_ptr(), n_, tiles_, b_, float(E_glob * ng_),
-                                   member_ss[k].data_ptr() if want else 0, member_ss[k].numel() if want else 0,
-                                   clip_ctl, slot.data_ptr(), C.addressof(spec_) if spec_ is not None else 0,
-                                   td_._ssac_logs.data_ptr() if spec_ is not None else 0,
-                                   cap.feed if last else 0, st))
+        last = cap is not None and cap.feed and m is members[-1] and (done_norm or want)
+        check(lib.ssac_critic_logs(m.log_parts.data_ptr(), m.log_nets, m.log_tiles, m.B, float(E_glob * m.n_glob),
+                                   ss_k.data_ptr() if want else 0, ss_k.numel() if want else 0, clip_ctl, slot.data_ptr(),
+                                   C.addressof(m.td_spec) if m.td_spec is not None else 0,
+                                   m.td_logs.data_ptr() if m.td_spec is not None else 0, cap.feed if last else 0, st))
         if last:
             cap.published = True
         done_norm = done_norm or want
     if not done_norm:
-        check(lib.ssac_group_norms(member_ss[k].data_ptr(), 1, member_ss[k].numel(), clip_ctl,
-                                   slot[lu.L_CRITIC_GN:].data_ptr(), st))
+        check(lib.ssac_group_norms(ss_k.data_ptr(), 1, ss_k.numel(), clip_ctl, slot[lu.L_CRITIC_GN:].data_ptr(), st))
     logs["gradients/critic_random_grad"] = slot[lu.L_CRITIC_GN]
     logs["gradients/encoder_criticloss_grad_norm"] = slot[lu.L_ENC_GN]
     if update_priorities:  # learning.py:139-140: advantage-based priorities on the LAST member's batch
-        lu.adjust_priorities(logs, replay_dicts[-1], agent, buffer)
-    return logs, replay_dicts
+        lu.adjust_priorities(logs, members[-1].rd, agent, buffer)
+    return logs, [m.rd for m in members]
+
+
+def _set_critic_input(m, c):
+    """m.X, m.ldx for the online critics under an identity encoder: [s | a] (continuous) or s (discrete)"""
+    (o, a), bt = m.rd["primary_batch"][:2], m.rd.get("_ssac")
+    s_rep = m.s_rep = lu.encode(c.agent.encoder, o)
+    if bt is not None and bt.xsa is not None and s_rep.data_ptr() == bt.xsa.data_ptr():
+        m.X, m.ldx = bt.xsa, bt.xsa.stride(0)
+    elif c.discrete:
+        m.X, m.ldx = s_rep, lu._row_stride(s_rep)
+    else:
+        x = m.X = lu._concat_buffer(c.ws, f"cu.x{m.i}", s_rep, a.shape[1])
+        x[:, s_rep.shape[1]:].copy_(a)
+        m.ldx = x.stride(0)
+
+
+def _member_targets(m, c):
+    """first pass over member m: batch, critic input, TD target, backup weights (requests in, outcomes out: MemberUpdate)"""
+    arena, ws, tag, agent = m.arena, c.ws, m.tag, c.agent
+    N, qd, H = arena.n_nets, arena.out_dim, arena.hidden
+    # when the merged actor / critic-forward launch will run, its workgroups fetch their own replay rows
+    # (ssac_gather) and the update has no gather launch
+    dual_ok = (DUAL_LAUNCH and arena.fused_dbuf and not c.train_enc and not c.dr3_coeff and not c.discrete
+               and _dual_fits(arena, c.batch_size) and not _split_forward(N, c.batch_size))
+    rd = m.rd = lu.sample_move_and_augment(buffer=c.buffer, batch_size=c.batch_size, augmenter=c.augmenter, aug_mix=c.aug_mix,
+                                           per=c.per, _defer_gather=dual_ok, _invariance=bool(c.encoder_lambda))
+    a, B = rd["primary_batch"][1], rd["primary_batch"][2].shape[0]
+    m.B = B
+    # The online critics' FORWARD does not depend on the TD target: on a second stream (a parallel graph
+    # branch) it overlaps the actor -> target critics -> TD-target chain, which occupies few CUs.
+    if arena.fused and not c.train_enc and not c.dr3_coeff and _split_forward(N, B):
+        _set_critic_input(m, c)
+        with engine.side_stream(c.dev, defer_join=True) as m.branch:
+            with engine._timed("critic_fwd"):
+                m.h1, m.h2, m.q = engine.mlp_forward(arena, m.X, m.ldx, 0, B, ws, tag)
+    if dual_ok and m.branch is None:
+        # the critics' forward rides in the actor's launch (when compute_td_targets uses the fused sample
+        # launch); the critic launch of the second pass is then only the backward half
+        _set_critic_input(m, c)
+        m.want_fwd = True
+        m.h1, m.h2, m.q = ws.get(tag + ".h1", (N, B, H)), ws.get(tag + ".h2", (N, B, H)), ws.get(tag + ".y", (N, B, qd))
+        if RANK1_BWD and qd == 1:
+            # and the TD-independent half (rank-1 loss gradient) of the backward pass rides in the target critics' launch
+            m.want_bwd, m.act, m.ld_act = True, a, a.stride(0)
+            m.dz2u, m.dz1u = ws.get(tag + ".dz2", (N, B, H)), ws.get(tag + ".dz1", (N, B, H))
+            # dz2u = W3 (.) [h2 > 0] need not leave the chained launch when the weight-gradient launch that follows
+            # is the loss-fold form: its fc2 tiles rebuild it from the saved h2 while staging (same values, bit for
+            # bit; 5 MB less written per update at the metric shape).  The chain launch reports whether it skipped.
+            m.dz2_optional = bool(SKIP_DZ2 and _loss_folds(B) and arena.shadow is None
+                                  and parallel.shard_of(agent) is None and H % 4 == 0)
+    m.lazy_td = bool(arena.fused and LAZY_TD and not c.dr3_coeff)
+    m.td, _ = lu.compute_td_targets(
+        logs=c.logs, replay_dict=rd, agent=agent, target_agent=c.target_agent, ensemble_idx=m.i, log_alphas=c.log_alphas,
+        ensemble_n=c.target_critic_ensemble_n, pop=c.pop, gamma=c.gamma, random_process=c.random_process,
+        noise_clip=c.noise_clip, discrete=c.discrete, _slot=c.slot, _member=m, _log_idx=m.ig)
+    lu.ensure_gathered(rd.get("_ssac"))  # (no-op when the merged launch took the gather)
+    c.all_rd.append(rd)
+    if c.sm_table is not None:
+        lu.member_sharded_softmax_scores(rd, agent, c.target_agent, c.ms, c.sm_table[m.ig])
+    m.bw = 1.0 if c.ms is not None else lu.compute_backup_weights(
+        logs=c.logs, replay_dict=rd, agent=agent, target_agent=c.target_agent, weight_type=c.weight_type,
+        weight_temp=c.weighted_bellman_temp, batch_size=c.batch_size, discrete=c.discrete, _slot=c.slot)
+
+
+def _encoder_input(m, c):
+    """online encoder WITH gradient (learning.py:83): the embedding goes straight into member m's critic input; returns
+    _encoder_step's `inv` (the invariance constraint's operands, or None)"""
+    agent, rd, ws, i, B = c.agent, m.rd, c.ws, m.i, m.B
+    o, a = rd["primary_batch"][:2]
+    xin = ws.get(f"cu.x{i}", (B, m.arena.in_dim))
+    inv = None
+    okey = getattr(agent.encoder, "ssac_obs_key", "obs")
+    # (the invariance constraint looks at the LAST member's batch only: learning.py:114-117 read the replay
+    # dict the member loop left behind)
+    lam_i = c.encoder_lambda if i == c.E - 1 else 0
+    if lam_i and rd["augmented_obs"][0][okey] is not o[okey]:
+        # encoder invariance on a partly augmented batch: the fully augmented observations need an encoder
+        # pass of their own WITH gradient -- one stacked 2B-row pass [o ; ao], whose backward then receives
+        # the critics' gradient in rows [0, B) and the constraint's in rows [B, 2B)
+        from . import conv_encoder
+        eng = conv_encoder.conv_engine(agent.encoder, c.dev)
+        img2 = ws.get("cu.img2", (2 * B,) + tuple(o[okey].shape[1:]))
+        img2[:B].copy_(o[okey])
+        img2[B:].copy_(rd["augmented_obs"][0][okey])
+        sall = ws.get("cu.sall", (2 * B, eng.emb))
+        eng.forward(img2, sall, eng.emb, True)
+        xin[:, :eng.emb].copy_(sall[:B])
+        s_rep, as_rep, stacked = xin[:, :eng.emb], sall[B:], True
+    else:
+        s_rep = lu.encode(agent.encoder, o, dst=xin, save=True)
+        as_rep, stacked = s_rep, False
+    if lam_i:
+        oo = rd["original_obs"][0]
+        if oo[okey] is o[okey]:
+            os_rep = ws.get("cu.osrep", (B, s_rep.shape[1]))
+            os_rep.copy_(s_rep)   # un-augmented batch: the target of the constraint is the embedding itself
+        else:
+            os_rep = lu.encode(agent.encoder, oo, dst=ws.get("cu.osrep", (B, s_rep.shape[1])), save=False)
+        inv = (as_rep, os_rep, c.encoder_lambda, stacked)
+        c.logs["encoder_constraint_loss"] = c.slot[lu.L_ENC_INV]
+    if not c.discrete:
+        xin[:, s_rep.shape[1]:].copy_(a)
+    m.s_rep, m.X, m.ldx = s_rep, xin, xin.stride(0)
+    return inv
+
+
+def _dr3_stacked(m, c, td, weight_ptr, pp, dopop, denom, a, B):
+    """DR3 (learning.py:100-108): the critics also run on (s', a'); both batches go through the per-layer
+    kernels as ONE stacked 2B-row batch, the co-adaptation gradient enters at the fc2 pre-activations"""
+    arena, rd, ws, tag, slot, st = m.arena, m.rd, c.ws, m.tag, c.slot, c.st
+    N, qd, H = arena.n_nets, arena.out_dim, arena.hidden
+    assert not c.train_enc and parallel.shard_of(c.agent) is None, "DR3 is supported for identity encoders on a single rank"
+    x1 = rd.get("_x1")
+    X1 = x1 if x1 is not None else lu.encode(c.target_agent.encoder, rd["primary_batch"][3])
+    Xc = ws.get(f"cu.xcat{m.i}", (2 * B, arena.in_dim))
+    Xc[:B].copy_(torch.as_strided(m.X, (B, arena.in_dim), (m.ldx, 1)))
+    Xc[B:].copy_(X1[:, :arena.in_dim])
+    ch1, ch2, cq = engine.mlp_forward(arena, Xc, arena.in_dim, 0, 2 * B, ws, tag + ".dr3", force_layers=True)
+    qc = ws.get(tag + ".dr3.qc", (N, B, qd))
+    qc.copy_(cq[:, :B])
+    dqc = ws.get(tag + ".dr3.dqc", (N, B, qd))
+    check(lib.ssac_critic_loss_bwd(qc.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), td.data_ptr(),
+                                   weight_ptr, pp, dopop, denom, dqc.data_ptr(), slot.data_ptr(), st))
+    dq2 = ws.get(tag + ".dr3.dq", (N, 2 * B, qd), zero=True)
+    dq2[:, :B].copy_(dqc)
+    dparts = ws.get(tag + ".dr3.parts", (int(lib.ssac_dr3_blocks()),))
+    coef = float(c.dr3_coeff) / denom / (N * B)
+
+    def dr3_hook(dz2_, _h2=ch2, _parts=dparts):
+        check(lib.ssac_dr3_add(dz2_.data_ptr(), _h2.data_ptr(), N, B, H, coef, _parts.data_ptr(), st))
+    engine.mlp_backward(arena, dq2, Xc, arena.in_dim, 0, ch1, ch2, 2 * B, ws, tag + ".dr3", adam=c.adam,
+                        adam_key=("critic", m.i), grads=m.grads, sumsq=m.ss, after_dz2=dr3_hook)
+    fca = dparts.sum() / (N * B)
+    c.logs[f"dr3_dotproduct_{m.i}"] = fca
+    # the logged overall loss includes the regulariser (learning.py:108, 133)
+    slot[lu.L_CRITIC_LOSS:lu.L_CRITIC_LOSS + 1].add_(fca * (float(c.dr3_coeff) / denom))
+
+
+def _lossfold_args(m, c, weight_ptr, pp, dopop, denom, B):
+    """engine.weight_grads(lossfold=...): dz2u / dz1u exist already; what depends on the TD target is one scalar per
+    (net, row), dL/dq, and the weight-gradient launch evaluates it itself (per workgroup, in LDS): no loss launch at all"""
+    arena, ws, slot, td, spec = m.arena, c.ws, c.slot, m.td, m.td_spec
+    lossfold = dict(q=m.q, td_ptr=0 if spec is not None else td.data_ptr(), spec_ptr=C.addressof(spec) if spec is not None else 0,
+                    weight_ptr=weight_ptr, popart_ptr=pp, pop=dopop, denom=denom, w3_snapshot=m.w3_snapshot,
+                    partials=ws.get(m.tag + ".fparts", (arena.n_nets * 2,)), dz2_from_h2=m.w3_snapshot is not None)
+    if arena.shadow is not None:
+        lossfold["bf"] = arena.bf_buffers(ws, "cu", B)
+    cap = engine.CAPTURE
+    if cap is not None and cap.deferred is not None and cap.deferred_chain and spec is not None:
+        cap.deferred_used = True
+        # recorded update: the launch leaves partials + TD statistics behind and advances the input ring;
+        # the next update's first launch (or a flush) writes the ring slot
+        late_ptr = cap.late or 0
+        if cap.late is not None:
+            cap.late_used = True
+            lossfold["late_target"] = cap.late_target.params
+            if arena.shadow is not None:
+                lossfold["target_shadow"] = cap.late_target.shadow
+        lossfold["logfold"] = _lib.LogFold(0, slot.data_ptr(), 0, cap.feed, cap.deferred.td_stats, late_ptr)
+    elif FOLD_LOGS and c.E_glob == 1 and not c.critic_clip:
+        # the log finalisation rides in the weight-gradient launch (its last workgroup to arrive): no logs launch
+        lossfold["logfold"] = _lib.LogFold(
+            ws.get("cu.done", (1,), dtype=torch.int32, zero=True).data_ptr(), slot.data_ptr(),
+            m.td_logs.data_ptr() if spec is not None else 0, cap.feed if (cap is not None and cap.feed) else 0, 0, 0)
+    return lossfold
+
+
+def _member_step(m, c):
+    """second pass over member m: loss gradient, backward, encoder step, weight gradient, in the form its record selects"""
+    arena, rd, i, ws, tag, slot, st, agent = m.arena, m.rd, m.i, c.ws, m.tag, c.slot, c.st, c.agent
+    N, qd, H, a, B = arena.n_nets, arena.out_dim, arena.hidden, rd["primary_batch"][1], m.B
+    td, bw, branch, train_enc = m.td, m.bw, m.branch, c.train_enc
+    # ---- the critics' input, weights and buffers
+    inv = _encoder_input(m, c) if train_enc else None
+    if m.X is None:
+        _set_critic_input(m, c)
+
+    def encoder_step(dX):
+        _encoder_step(agent.encoder, c.encoder_optimizer, c.encoder_clip, dX, m.s_rep.shape[1], ws, slot, c.dev, inv,
+                      accumulate=i > 0, step=i == c.E - 1)
+    if c.encoder_lambda and not train_enc:
+        # identity encoder: augmented == original observations (only the identity augmentation applies to vectors),
+        # the constraint is exactly zero and has no parameter to reach (learning_utils.py:401-409)
+        c.logs["encoder_constraint_loss"] = slot[lu.L_ENC_INV]
+    X, ldx = m.X, m.ldx
+    shard = parallel.shard_of(agent)
+    n_glob = m.n_glob = N if shard is None else shard.num_critics  # loss is averaged over the GLOBAL ensemble
+    denom = float(c.E_glob * n_glob)
+    popart = agent.popart[i]
+    weight_ptr = 0 if isinstance(bw, float) else bw.data_ptr()  # imp_weights is ones(1) on the uniform path
+    if c.per:
+        # learning.py:96-98 multiplies (B,1) errors by the (B,) importance weights: a (B,B) outer product
+        # whose mean is mean(w) * mean(bw * err^2) -- i.e. every row's weight is scaled by mean(w)
+        wrow = ws.get(f"cu.w{i}", (B, 1))
+        scale = rd["imp_weights"].mean().to(torch.float32)
+        if isinstance(bw, float):
+            wrow.fill_(1.0)
+        else:
+            wrow.copy_(bw.view(B, 1))
+        wrow.mul_(scale)
+        weight_ptr = wrow.data_ptr()
+    pp, dopop = (popart.ptr if popart else 0), (1 if (popart and c.pop) else 0)
+    ttot = engine.bf16_tiles_total(arena) if arena.shadow is not None else engine.wgrad_tiles_total(arena)
+    ss = m.ss = ws.get(f"cu.ss{i}", (N * ttot,))
+    dq = ws.get(f"cu.dq{i}", (N, B, qd))
+    grads = m.grads = ws.get(f"cu.g{i}", (arena.params.numel(),), zero=True) if c.critic_clip else None
+    fused_form = arena.fused and not c.dr3_coeff
+    if fused_form:
+        dz2, dz1 = ws.get(tag + ".dz2", (N, B, H)), ws.get(tag + ".dz1", (N, B, H))
+        tiles = int(lib.ssac_fused_row_tiles(C.byref(arena.desc()), B, N))
+        parts = ws.get(tag + ".parts", (N * tiles * 2,))
+        spec_ptr = C.addressof(m.td_spec) if m.td_spec is not None else 0  # the TD target is evaluated inside the critic launch
+    if m.w3_snapshot is not None and not (m.bwd_done and _loss_folds(B)):
+        raise RuntimeError("internal: the chained launch skipped dz2u but no loss-fold weight-gradient launch follows")
+    # ---- the launch form (a merged launch of the first pass implies arena.fused and no DR3)
+    lossfold = None
+    if c.dr3_coeff:
+        _dr3_stacked(m, c, td, weight_ptr, pp, dopop, denom, a, B)
+    elif m.bwd_done and _loss_folds(B):
+        lossfold = _lossfold_args(m, c, weight_ptr, pp, dopop, denom, B)
+    elif m.bwd_done:
+        # rank-1 backward done: a single-workgroup launch writes the N x B scalars dL/dq for the weight-gradient launch to read
+        loss_bwd, td_arg = ((lib.ssac_critic_loss_bwd_lazy, spec_ptr) if m.td_spec is not None else
+                            (lib.ssac_critic_loss_bwd, td.data_ptr()))
+        check(loss_bwd(m.q.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), td_arg, weight_ptr, pp, dopop, denom,
+                       dq.data_ptr(), slot.data_ptr(), st))
+    elif branch is not None or m.fwd_done:
+        # loss gradient + head backward + backward-data on the saved forward: ONE launch
+        if branch is not None:
+            branch.join()
+        with engine._timed("critic_bwd") as tm:
+            for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
+                check(lib.ssac_critic_bwd_fused(
+                    C.byref(arena.desc()), B, td.data_ptr(), weight_ptr, a.data_ptr(), a.stride(0), pp, dopop, denom,
+                    m.h1.data_ptr(), m.h2.data_ptr(), m.q.data_ptr(), dq.data_ptr(), dz2.data_ptr(), dz1.data_ptr(),
+                    parts.data_ptr(), spec_ptr, st))
+    elif arena.fused:
+        # forward of all N critics + loss gradient + backward-data: ONE launch
+        m.h1, m.h2, m.q = ws.get(tag + ".h1", (N, B, H)), ws.get(tag + ".h2", (N, B, H)), ws.get(tag + ".y", (N, B, qd))
+        with engine._timed("critic_fused") as tm:
+            for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
+                check(lib.ssac_critic_fwd_bwd_fused(
+                    C.byref(arena.desc()), X.data_ptr(), ldx, B, td.data_ptr(), weight_ptr, a.data_ptr(),
+                    a.stride(0), pp, dopop, denom, m.h1.data_ptr(), m.h2.data_ptr(), m.q.data_ptr(),
+                    dq.data_ptr(), dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), spec_ptr, st))
+    else:  # the per-layer family
+        if arena.shadow is not None:
+            raise NotImplementedError("bf16 mode needs the fused kernel family (hidden % 32 == 0, <= 256)")
+        h1, h2, q = engine.mlp_forward(arena, X, ldx, 0, B, ws, tag)
+        check(lib.ssac_critic_loss_bwd(q.data_ptr(), N, B, qd, a.data_ptr(), a.stride(0), td.data_ptr(), weight_ptr, pp,
+                                       dopop, denom, dq.data_ptr(), slot.data_ptr(), st))
+        if train_enc:
+            dX = engine.mlp_backward(arena, dq, X, ldx, 0, h1, h2, B, ws, tag, need_dx=True, update=False)
+            encoder_step(dX)
+            dz2, dz1 = ws.get(tag + ".dz2", (N, B, arena.hidden)), ws.get(tag + ".dz1", (N, B, arena.hidden))
+            engine.weight_grads(arena, X, ldx, 0, h1, h2, dq, dz2, dz1, B, adam=c.adam, adam_key=("critic", i), grads=grads, sumsq=ss)
+        else:
+            engine.mlp_backward(arena, dq, X, ldx, 0, h1, h2, B, ws, tag, adam=c.adam, adam_key=("critic", i), grads=grads, sumsq=ss)
+    if not fused_form:
+        return
+    # ---- the fused forms' common tail: encoder step, weight gradients, what the log launch will read
+    if train_enc:  # dL/d(embedding) = sum over critics of dz1 W1[:, :emb], BEFORE W1 is updated
+        dX = ws.get(tag + ".dx", (N, B, arena.in_dim))
+        check(lib.ssac_mlp_layer_dgrad(C.byref(arena.desc()), 0, 0, N, dz1.data_ptr(), H, B * H, 0, 0, 0,
+                                       B, dX.data_ptr(), arena.in_dim, B * arena.in_dim, st))
+        encoder_step(dX)
+    if arena.shadow is not None and lossfold is None:
+        raise NotImplementedError(
+            "bf16 mode covers the chained critic update (continuous single-output critics, stochastic actor, "
+            "identity encoder, with or without PopArt / gradient clipping; no DR3, no discrete critics)")
+    m.logs_folded = bool(engine.weight_grads(
+        arena, X, ldx, 0, m.h1, m.h2, dq, dz2, dz1, B, adam=c.adam, adam_key=("critic", i), grads=grads, sumsq=ss,
+        rowscale=dq if (m.bwd_done and lossfold is None) else None, lossfold=lossfold,
+        target=lossfold.get("late_target") if lossfold is not None else None))
+    if m.logs_folded and lossfold["logfold"].feed:
+        engine.CAPTURE.published = True
+    m.log_parts, m.log_nets, m.log_tiles = ((lossfold["partials"], N, 1) if lossfold is not None else
+                                            (parts, 0 if m.bwd_done else N, tiles))
 
 
 def _actor_chain_form(a_arena, A, B, c_arena):

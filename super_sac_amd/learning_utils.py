@@ -6,6 +6,7 @@ Every arithmetic step is a kernel of libssac_hip.so; this file only sequences la
 keeps the reference's host-RNG order (index draw -> augmentation draw -> action noise ->
 REDQ subset).
 """
+import collections
 import ctypes as C
 import os
 import math
@@ -260,6 +261,33 @@ class _Batch:
     __slots__ = ("B", "S", "A", "xsa", "x1sa", "r", "d", "key", "pixel", "pending")
 
 
+class MemberUpdate:
+    """what ONE ensemble member's critic update passes between its launches: learning._critic_update_eager makes one per
+    member, compute_td_targets and the launchers below fill it in, a recording keeps its records alive.  Identity: i / ig
+    (local / global member index), arena (critics), tag (workspace), rd (replay dict), B (rows).  Requests, set before
+    compute_td_targets runs: want_fwd -- the online critics' forward may ride in the actor launch (s_rep, X, ldx, h1, h2,
+    q); want_bwd -- the TD-independent backward may ride in the target launch (act, ld_act, dz2u, dz1u); dz2_optional --
+    dz2u may stay inside the chained launch; lazy_td -- the TD target is left to the critic launch.  Outcomes, set by the
+    launch that did the work: fwd_done, bwd_done; w3_snapshot (W3 as the chained launch saw it when it skipped dz2u, else
+    None); chain (arguments of a PENDING chained launch, None once issued); td with td_spec (ssac_td_spec; None: evaluated
+    already), td_logs (its log words), td_keep (tensors the spec points into); bw (backup weights); branch (side stream);
+    ss, grads, log_parts / log_nets / log_tiles, n_glob, logs_folded: what the clip and log launches read."""
+    __slots__ = ("i", "ig", "arena", "tag", "rd", "B", "want_fwd", "s_rep", "X", "ldx", "h1", "h2", "q", "want_bwd", "act",
+                 "ld_act", "dz2u", "dz1u", "dz2_optional", "lazy_td", "fwd_done", "bwd_done", "w3_snapshot", "chain", "td",
+                 "td_spec", "td_logs", "td_keep", "bw", "branch", "ss", "grads", "log_parts", "log_nets", "log_tiles",
+                 "n_glob", "logs_folded")
+
+    def __init__(self, i, ig, arena):
+        for f in self.__slots__:
+            setattr(self, f, None)
+        self.i, self.ig, self.arena, self.tag = i, ig, arena, f"cu.c{i}"
+        self.want_fwd = self.want_bwd = self.dz2_optional = self.lazy_td = self.fwd_done = self.bwd_done = False
+
+
+# target-critic outputs of a REDQ subset: q (n * parts, B, out); xchg_done: reduced over the critic-sharded ranks already
+SubsetQ = collections.namedtuple("SubsetQ", "q n parts xchg_done", defaults=(1, False))
+
+
 # actor sample -> target critics chained per workgroup, beside the critics' forward + unscaled backward: ONE launch
 CHAIN_LAUNCH = True
 # the chained launch in its producer / consumer form (the actor once per tile, the target critics start before a' exists);
@@ -510,16 +538,13 @@ def _upload_ids(ws, ids, device, tag):
 
 
 def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ensemble_n, log_alphas,
-                       pop, gamma, random_process, noise_clip, discrete=False, _slot=None, _defer=False,
-                       _co_forward=None, _co_backward=None, _log_idx=None):
-    """learning_utils.py:298-354.  With ``_defer`` (critic_update's fused path; continuous actions, no PopArt)
-    the final elementwise step -- and its three log values -- is not launched here: the returned ``td`` buffer
-    carries a ``_ssac_spec`` (ssac_td_spec) and the critic launch evaluates the targets into it.
-    ``_co_forward`` = (critic arena, X, ldx, h1, h2, q): when the actor runs as the fused sample launch, the online
-    critics' forward rides in the SAME launch (ssac_actor_sample_critic_fwd); replay_dict["_co_fwd"] is then True.
-    ``_co_backward`` = (critic arena, h1, h2, act, ld_act, dz2u, dz1u): after such a forward, the TD-independent half
-    of the critics' backward pass rides in the target critics' launch (ssac_target_fwd_critic_bwdu);
-    replay_dict["_co_bwd"] is then True."""
+                       pop, gamma, random_process, noise_clip, discrete=False, _slot=None, _member=None, _log_idx=None):
+    """learning_utils.py:298-354.  ``_member`` (critic_update only): the member's MemberUpdate record.  Its requests let
+    launches here take over the online critics' forward (ssac_actor_sample_critic_fwd) and the TD-independent half of their
+    backward pass (ssac_target_fwd_critic_bwdu), and leave the final elementwise step with its three log values to the
+    critic launch (``td_spec``; continuous actions, no PopArt); its outcomes say which of them did."""
+    m = _member
+    co_fwd = m if (m is not None and m.want_fwd) else None
     o, a, r, o1, d = replay_dict["primary_batch"]
     i = ensemble_idx
     dev = r.device
@@ -541,11 +566,11 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     a_arena = engine.bind_arena(actor, "self", [actor], dev)
     fuse_sample = kind == "stochastic" and a_arena.fused and random_process is None
     # actor -> target critics chained inside one launch with the critics' forward + TD-independent backward
-    chain = ({} if (CHAIN_LAUNCH and fuse_sample and _co_forward is not None and _co_backward is not None
-                    and (parallel_shard_of(target_agent) is None or engine.CAPTURE is not None)
-                    and target_agent.critics[i].arena(dev).fused_dbuf
-                    and target_agent.critics[i].arena(dev).out_dim == 1) else None)
-    if not (fuse_sample and _co_forward is not None):
+    chain = (CHAIN_LAUNCH and fuse_sample and co_fwd is not None and m.want_bwd
+             and (parallel_shard_of(target_agent) is None or engine.CAPTURE is not None)
+             and target_agent.critics[i].arena(dev).fused_dbuf
+             and target_agent.critics[i].arena(dev).out_dim == 1)
+    if not (fuse_sample and co_fwd is not None):
         ensure_gathered(replay_dict.get("_ssac"))  # (a deferred replay gather rides in the merged launch only)
     if not fuse_sample:
         _, _, aout = engine.mlp_forward(a_arena, s1_rep, _row_stride(s1_rep), 0, B, ws, f"td.a{i}",
@@ -560,7 +585,7 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     use_entropy = 0
     if kind == "discrete":
         ids = draw_subset(N, ensemble_n)
-        q1, n_q = _subset_q(ws, shard, t_arena, ids, s1_rep, _row_stride(s1_rep), B, dev, f"td.c{i}")
+        sq = _subset_q(ws, shard, t_arena, ids, s1_rep, _row_stride(s1_rep), B, dev, f"td.c{i}")
         lp_ptr, qd = aout.data_ptr(), t_arena.out_dim
         a_s1 = None
     else:
@@ -591,18 +616,16 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
                 rs = _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset) if cap is not None else _lib.Rng(ns[0], 0, ns[1])
                 if cap is None:
                     ns[1] += 1
-                _actor_sample(a_arena, s1_rep, B, 0, actor, x1, S, A, logp, C.addressof(rs), st, _co_forward,
+                _actor_sample(a_arena, s1_rep, B, 0, actor, x1, S, A, logp, C.addressof(rs), st, co_fwd,
                               replay_dict, chain=chain, rng_keep=rs)
                 eps = None
             else:
                 eps = draw_normal((B, A), dev)
-            if eps is None:
-                pass
-            elif fuse_sample:
+            if eps is not None and fuse_sample:
                 # actor forward + sample + log pi: ONE launch, a' lands in the [s'|a'] buffer
-                _actor_sample(a_arena, s1_rep, B, eps.data_ptr(), actor, x1, S, A, logp, 0, st, _co_forward,
+                _actor_sample(a_arena, s1_rep, B, eps.data_ptr(), actor, x1, S, A, logp, 0, st, co_fwd,
                               replay_dict, chain=chain, rng_keep=eps)
-            else:
+            elif eps is not None:
                 check(lib.ssac_tanh_normal_fwd(aout.data_ptr(), 2 * A, eps.data_ptr(), B, A,
                                                float(actor.log_std_low), float(actor.log_std_high),
                                                x1.data_ptr(), S + A, S, logp.data_ptr(), st))
@@ -628,20 +651,20 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
                 check(lib.ssac_det_logprob(0, B, A, logp.data_ptr(), st))
                 use_entropy = 1
         ids = draw_subset(N, ensemble_n)
-        cob = _co_backward if replay_dict.get("_co_fwd") else None
-        q1, n_q = _subset_q(ws, shard, t_arena, ids, x1, S + A, B, dev, f"td.c{i}", co_backward=cob,
-                            replay_dict=replay_dict)
+        sq = _subset_q(ws, shard, t_arena, ids, x1, S + A, B, dev, f"td.c{i}", m)
+        assert m is None or m.chain is None, "a chained launch is still pending"
         lp_ptr, qd = logp.data_ptr(), 1
         a_s1 = x1[:, S:]
+    q1 = sq.q
     td = torch.empty(B, 1, device=dev)
-    if _defer and qd == 1 and not popart:
-        td._ssac_spec = _lib.TdSpec(q1.data_ptr(), lp_ptr, r.data_ptr(), d.data_ptr(), log_alpha.data_ptr(),
-                                    td.data_ptr(), float(gamma), n_q, use_entropy, int(getattr(q1, "_ssac_parts", 1)))
-        td._ssac_logs = slot[L_TD0 + 3 * i:]
-        td._ssac_keep = (q1, logp, r, d, log_alpha)
+    if m is not None and m.lazy_td and qd == 1 and not popart:
+        m.td_spec = _lib.TdSpec(q1.data_ptr(), lp_ptr, r.data_ptr(), d.data_ptr(), log_alpha.data_ptr(),
+                                td.data_ptr(), float(gamma), sq.n, use_entropy, sq.parts)
+        m.td_logs = slot[L_TD0 + 3 * i:]
+        m.td_keep = (q1, logp, r, d, log_alpha)
     else:
-        assert getattr(q1, "_ssac_parts", 1) == 1, "partial target Q needs the in-launch TD target (ssac_td_spec.n_parts)"
-        check(lib.ssac_td_target(q1.data_ptr(), n_q, B, qd, lp_ptr, r.data_ptr(), d.data_ptr(),
+        assert sq.parts == 1, "partial target Q needs the in-launch TD target (ssac_td_spec.n_parts)"
+        check(lib.ssac_td_target(q1.data_ptr(), sq.n, B, qd, lp_ptr, r.data_ptr(), d.data_ptr(),
                                  log_alpha.data_ptr(), use_entropy, float(gamma),
                                  popart.ptr if popart else 0, 1 if (popart and pop) else 0,
                                  td.data_ptr(), slot[L_TD0 + 3 * i:].data_ptr(), st))
@@ -656,21 +679,20 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     return td, (s1_rep, a_s1)
 
 
-def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, st, co_forward, replay_dict,
-                  chain=None, rng_keep=None):
-    """actor forward + tanh-normal sample + log pi in ONE launch (a' lands in the [s'|a'] buffer), optionally with
-    the online critics' forward as extra workgroups of the same launch."""
+def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, st, m, replay_dict,
+                  chain=False, rng_keep=None):
+    """actor forward + tanh-normal sample + log pi in ONE launch (a' lands in the [s'|a'] buffer), optionally -- m, the
+    member's record, asks for it -- with the online critics' forward as extra workgroups of the same launch."""
     bt = replay_dict.get("_ssac")
-    if co_forward is not None and chain is not None:
+    if m is not None and chain:
         # the whole TD-independent part of the update is ONE launch (ssac_chain_update), issued by _subset_q once the
         # REDQ subset is known: nothing is launched here
-        chain.update(a_arena=a_arena, s1_rep=s1_rep, eps_ptr=eps_ptr, actor=actor, x1=x1, S=S, A=A, logp=logp,
-                     rng_ptr=rng_ptr, rng_keep=rng_keep, co_forward=co_forward)
-        replay_dict["_chain"] = chain
-        replay_dict["_co_fwd"] = True
+        m.chain = dict(a_arena=a_arena, s1_rep=s1_rep, eps_ptr=eps_ptr, actor=actor, x1=x1, S=S, A=A, logp=logp,
+                       rng_ptr=rng_ptr, rng_keep=rng_keep)
+        m.fwd_done = True
         return
-    if co_forward is not None:
-        c_arena, X, ldx, h1, h2, q = co_forward
+    if m is not None:
+        c_arena, X, ldx, h1, h2, q = m.arena, m.X, m.ldx, m.h1, m.h2, m.q
         gth = None
         if (bt is not None and bt.pending is not None and x1.data_ptr() == bt.x1sa.data_ptr()
                 and X.data_ptr() == bt.xsa.data_ptr()):
@@ -684,7 +706,7 @@ def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, s
                     float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S, logp.data_ptr(),
                     rng_ptr, C.byref(c_arena.desc()), X.data_ptr(), ldx, h1.data_ptr(), h2.data_ptr(),
                     q.data_ptr(), C.byref(gth) if gth is not None else 0, st))
-        replay_dict["_co_fwd"] = True
+        m.fwd_done = True
         return
     ensure_gathered(bt)
     check(lib.ssac_actor_sample_fused(C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, eps_ptr,
@@ -697,12 +719,12 @@ def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, s
 FUSE_XCHG = True
 
 
-def _launch_chain(ch, co_backward, t_arena, ids_ptr, n, ws, tag, B, replay_dict, allow_split=True, xchg=None):
-    """ssac_chain_update: the deferred actor sample (ch, from _actor_sample), the target critics of the n subset slots
-    and the online critics' forward + TD-independent backward, ONE launch; returns the target outputs (n, B, 1)"""
-    c_arena, h1, h2, act, ld_act, dz2u, dz1u = co_backward
-    _, Xc, ldxc, _, _, qc = ch["co_forward"]
-    bt = replay_dict.get("_ssac")
+def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=None):
+    """ssac_chain_update: the pending actor sample (m.chain, from _actor_sample), the target critics of the n subset
+    slots and the online critics' forward + TD-independent backward, ONE launch; returns the target outputs as a SubsetQ"""
+    ch, m.chain = m.chain, None
+    c_arena, h1, h2, dz2u, dz1u, Xc, ldxc, qc = m.arena, m.h1, m.h2, m.dz2u, m.dz1u, m.X, m.ldx, m.q
+    bt = m.rd.get("_ssac")
     x1, S, A, actor = ch["x1"], ch["S"], ch["A"], ch["actor"]
     gth = None
     if (bt is not None and bt.pending is not None and x1.data_ptr() == bt.x1sa.data_ptr()
@@ -722,14 +744,12 @@ def _launch_chain(ch, co_backward, t_arena, ids_ptr, n, ws, tag, B, replay_dict,
         splits = int(lib.ssac_chain_target_splits(C.byref(ch["a_arena"].desc()), C.byref(t_arena.desc()),
                                                   C.byref(c_arena.desc()), B, n))
     q1 = ws.get(tag + ".y", (n * splits, B, 1))
-    q1._ssac_parts = splits
     s1_rep = ch["s1_rep"]
-    cap = engine.CAPTURE
     dl_ptr = 0
-    if cap is not None and cap.feed and cap.deferred is not None:
+    if cap_ is not None and cap_.feed and cap_.deferred is not None:
         # recorded update: one extra workgroup of this launch writes the PREVIOUS update's log block to its ring slot
-        dl_ptr = C.addressof(cap.deferred)
-        cap.deferred_chain = True
+        dl_ptr = C.addressof(cap_.deferred)
+        cap_.deferred_chain = True
     if c_arena.shadow is not None:
         # bf16-operand mode: the same launch on v_mfma_f32_32x32x16_bf16, fed from the arenas' bf16 shadows
         a_arena = ch["a_arena"]
@@ -748,9 +768,9 @@ def _launch_chain(ch, co_backward, t_arena, ids_ptr, n, ws, tag, B, replay_dict,
                     bf["h1t"].data_ptr(), bf["h2t"].data_ptr(), bf["dz2t"].data_ptr(), bf["dz1t"].data_ptr(),
                     bf["xt"].data_ptr(), C.byref(gth) if gth is not None else 0, dl_ptr,
                     ho.data_ptr() if ho is not None else 0, engine.stream()))
-        replay_dict["_co_bwd"] = True
-        return q1
-    skip_dz2 = bool(replay_dict.pop("_dz2_optional", False))
+        m.bwd_done = True
+        return SubsetQ(q1, n, splits)
+    skip_dz2 = m.dz2_optional
     # (the head rows W3 as THIS launch sees them: the weight-gradient launch that rebuilds dz2u from h2 cannot read the
     #  arena's W3 -- its own head workgroups are updating it while the fc2 tiles run)
     w3s = ws.get(tag + ".w3s", (c_arena.n_nets, c_arena.hidden))
@@ -767,37 +787,38 @@ def _launch_chain(ch, co_backward, t_arena, ids_ptr, n, ws, tag, B, replay_dict,
                 qc.data_ptr(), 0 if skip_dz2 else dz2u.data_ptr(), dz1u.data_ptr(), w3s.data_ptr(),
                 C.byref(gth) if gth is not None else 0, dl_ptr, ho.data_ptr() if ho is not None else 0, splits,
                 xchg.handle if (xchg is not None and ho is not None) else 0, engine.stream()))
-    q1._ssac_xchg_done = xchg is not None and ho is not None   # (the launch reduced q1 over the ranks itself)
     if skip_dz2:
-        replay_dict["_dz2_skipped"] = w3s   # (the weight-gradient launch rebuilds dz2u from h2 and this W3 copy)
-    replay_dict["_co_bwd"] = True
-    return q1
+        m.w3_snapshot = w3s   # (the weight-gradient launch rebuilds dz2u from h2 and this W3 copy)
+    m.bwd_done = True
+    return SubsetQ(q1, n, splits, xchg is not None and ho is not None)  # (... the launch reduced q1 over the ranks itself)
 
 
-def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, co_backward=None, replay_dict=None):
-    """target-critic outputs for the REDQ subset `ids`: (q, n) with q of shape (n, B, out).
-    Sharded: forward of the locally owned subset members, elementwise min, MIN all-reduce of the
-    (B x out) partial (the one real exchange step of the critic update), n = 1."""
+def _target_fwd_critic_bwdu(m, t_arena, ids_ptr, n, X, ldx, B, q1):
+    """the n subset slots' target critics with the TD-independent half of member m's backward pass: ONE launch"""
+    check(lib.ssac_target_fwd_critic_bwdu(
+        C.byref(t_arena.desc()), ids_ptr, n, X.data_ptr(), ldx, B, q1.data_ptr(), C.byref(m.arena.desc()), m.h1.data_ptr(),
+        m.h2.data_ptr(), m.act.data_ptr(), m.ld_act, m.dz2u.data_ptr(), m.dz1u.data_ptr(), engine.stream()))
+    m.bwd_done = True
+
+
+def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, m=None):
+    """target-critic outputs for the REDQ subset `ids`: SubsetQ(q, n, ...) with q of shape (n, B, out).  Sharded: forward of
+    the locally owned subset members, elementwise min, MIN all-reduce of the (B x out) partial (the one real exchange step
+    of the critic update), n = 1.  m: the member's record -- its pending chained launch or ridden backward is issued here."""
+    ride = m is not None and m.want_bwd and m.fwd_done
     if shard is None:
         ids_dev = _upload_ids(ws, ids, dev, "sub")
-        ch = replay_dict.pop("_chain", None) if replay_dict is not None else None
-        if ch is not None:
-            q1 = _launch_chain(ch, co_backward, t_arena, ids_dev.data_ptr(), len(ids), ws, tag, B, replay_dict)
-            return q1, len(ids)
-        if co_backward is not None and t_arena.fused_dbuf:
-            c_arena, h1, h2, act, ld_act, dz2u, dz1u = co_backward
+        if m is not None and m.chain is not None:
+            return _launch_chain(m, t_arena, ids_dev.data_ptr(), len(ids), ws, tag, B)
+        if ride and t_arena.fused_dbuf:
             q1 = ws.get(tag + ".y", (len(ids), B, t_arena.out_dim))
             with engine._timed("dual_bwd") as tm:
                 for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
-                    check(lib.ssac_target_fwd_critic_bwdu(
-                        C.byref(t_arena.desc()), ids_dev.data_ptr(), len(ids), X.data_ptr(), ldx, B, q1.data_ptr(),
-                        C.byref(c_arena.desc()), h1.data_ptr(), h2.data_ptr(), act.data_ptr(), ld_act,
-                        dz2u.data_ptr(), dz1u.data_ptr(), engine.stream()))
-            replay_dict["_co_bwd"] = True
-            return q1, len(ids)
+                    _target_fwd_critic_bwdu(m, t_arena, ids_dev.data_ptr(), len(ids), X, ldx, B, q1)
+            return SubsetQ(q1, len(ids))
         _, _, q1 = engine.mlp_forward(t_arena, X, ldx, 0, B, ws, tag, net_ids=ids_dev, n_sel=len(ids),
                                       save=False)
-        return q1, len(ids)
+        return SubsetQ(q1, len(ids))
     from . import parallel
     O = t_arena.out_dim
     qpart = ws.get(tag + ".qpart", (1, B, O))
@@ -806,26 +827,22 @@ def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, co_backward=None, re
         # recorded launch sequence: a fixed shape for every subset draw -- all len(ids) slots are forwarded, the
         # per-update device id block holds the LOCAL index of the members this rank owns and -1 for the others
         # (their outputs are +inf), and the collective runs between two recorded segments
-        n = len(ids)
-        ch = replay_dict.pop("_chain", None) if replay_dict is not None else None
-        if ch is not None:
+        n, parts = len(ids), 1
+        if m is not None and m.chain is not None:
             # (partial sums only when the one-shot exchange will carry them: it sums a slot's parts before sending)
-            x_ = parallel._exchange if (FUSE_XCHG and parallel._exchange is not None and ch["a_arena"].shadow is None
+            x_ = parallel._exchange if (FUSE_XCHG and parallel._exchange is not None
+                                        and m.chain["a_arena"].shadow is None
                                         and n * B <= parallel._exchange.max_floats) else None
-            q1 = _launch_chain(ch, co_backward, t_arena, cap.ids_dev.data_ptr(), n, ws, tag, B, replay_dict,
+            sq = _launch_chain(m, t_arena, cap.ids_dev.data_ptr(), n, ws, tag, B,
                                allow_split=parallel._exchange is not None, xchg=x_)
-            if getattr(q1, "_ssac_xchg_done", False):
+            if sq.xchg_done:
                 parallel.check_exchange()   # (of the exchanges issued so far: a host load, as all_reduce_min_owned does)
-                return q1, n
-        elif co_backward is not None and t_arena.fused_dbuf:
+                return sq
+            q1, parts = sq.q, sq.parts
+        elif ride and t_arena.fused_dbuf:
             # ... and the TD-independent half of the local critics' backward pass rides in the same launch
-            c_arena, h1, h2, act, ld_act, dz2u, dz1u = co_backward
             q1 = ws.get(tag + ".y", (n, B, O))
-            check(lib.ssac_target_fwd_critic_bwdu(
-                C.byref(t_arena.desc()), cap.ids_dev.data_ptr(), n, X.data_ptr(), ldx, B, q1.data_ptr(),
-                C.byref(c_arena.desc()), h1.data_ptr(), h2.data_ptr(), act.data_ptr(), ld_act, dz2u.data_ptr(),
-                dz1u.data_ptr(), engine.stream()))
-            replay_dict["_co_bwd"] = True
+            _target_fwd_critic_bwdu(m, t_arena, cap.ids_dev.data_ptr(), n, X, ldx, B, q1)
         else:
             _, _, q1 = engine.mlp_forward(t_arena, X, ldx, 0, B, ws, tag, net_ids=cap.ids_dev, n_sel=n, save=False)
         # MIN all-reduce of all n slots at once (n x B x O floats; slots this rank does not own hold +inf): the minimum
@@ -833,11 +850,11 @@ def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, co_backward=None, re
         if parallel.one_shot_ready(q1):
             # ONE recorded launch (csrc/ssac_xchg.hip): the update stays one launch list; only the subset members'
             # owners send (the id block, mirrored to device memory by the update's first launch, names them)
-            parallel.all_reduce_min_owned(q1, cap.ids_dev, n, int(getattr(q1, "_ssac_parts", 1)))
+            parallel.all_reduce_min_owned(q1, cap.ids_dev, n, parts)
         else:
-            assert getattr(q1, "_ssac_parts", 1) == 1
+            assert parts == 1
             cap.collective(lambda: parallel.all_reduce_min(q1))
-        return q1, n
+        return SubsetQ(q1, n, parts)
     local = shard.local_subset(ids)
     if local:
         ids_dev = _upload_ids(ws, local, dev, f"sub{len(local)}")
@@ -847,7 +864,7 @@ def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, co_backward=None, re
     else:
         qpart.fill_(float("inf"))
     parallel.all_reduce_min(qpart)
-    return qpart, 1
+    return SubsetQ(qpart, 1)
 
 
 # ------------------------------------------------------------------------------------------

@@ -320,6 +320,60 @@ def test_graph_replay_equals_eager_launches():
     assert le[0] == lg[0] and le[1] == lg[1]
 
 
+@pytest.mark.parametrize("setting", ["eager", "no-dual-launch", "no-rank1-backward", "no-loss-fold", "recorded-list"])
+def test_critic_update_hands_back_no_private_launch_state(setting):
+    """which launch did which part of a member's update travels in the member's record, not in what the caller gets
+    back: the replay dicts hold no private key but "_ssac", "_subset", "_x1", and the TD target is a plain tensor.
+    (obs 17 / act 6 / hidden 64 / 4 critics / subset 2 / B 128: the smallest shape at which every merged launch
+    form is still eligible; recorded-list runs 5 calls past the warm-up, so the fast C step hands back the dicts too)"""
+    import copy
+    import math
+    import random
+    from itertools import chain
+
+    import torch
+    import super_sac_amd as ssa
+
+    L = ssa.learning
+    knob = {"no-dual-launch": "DUAL_LAUNCH", "no-rank1-backward": "RANK1_BWD", "no-loss-fold": "FOLD_LOSS"}.get(setting)
+    recorded = setting == "recorded-list"
+    old = (L.USE_GRAPHS, L.LAUNCH_MODE, L.DUAL_LAUNCH, L.RANK1_BWD, L.FOLD_LOSS)
+    L.USE_GRAPHS, L.LAUNCH_MODE = recorded, "list"
+    if knob is not None:
+        setattr(L, knob, False)
+    try:
+        torch.manual_seed(3); np.random.seed(3); random.seed(3)
+        dev = torch.device("cuda")
+        agent = ssa.Agent(act_space_size=6, encoder=ssa.nets.IdentityEncoder(17),
+                          actor_network_cls=ssa.nets.ContinuousStochasticActor,
+                          critic_network_cls=ssa.nets.ContinuousCritic, ensemble_size=1, num_critics=4,
+                          hidden_size=64, auto_rescale_targets=False, log_std_low=-5.0, log_std_high=2.0)
+        agent.to(dev)
+        target = copy.deepcopy(agent)
+        buf = ssa.replay.ReplayBuffer(4096, device=dev)
+        buf.load_experience(*synth.synth_transitions(2000, 17, 6, seed=5))
+        copt = torch.optim.Adam(chain(*(c.parameters() for c in agent.critics)), lr=3e-4)
+        eopt = torch.optim.Adam(agent.encoder.parameters(), lr=1e-4)
+        la = torch.Tensor([math.log(0.1)]).to(dev); la.requires_grad = True
+        aug = ssa.augmentations.AugmentationSequence([ssa.augmentations.IdentityAug(128)])
+        for k in range(L.GRAPH_WARMUP + 1 + 5 if recorded else 2):
+            _, dicts = L.critic_update(
+                buffer=buf, agent=agent, target_agent=target, critic_optimizer=copt, encoder_optimizer=eopt,
+                log_alphas=[la], batch_size=128, gamma=0.99, critic_clip=None, encoder_clip=None,
+                target_critic_ensemble_n=2, weighted_bellman_temp=None, weight_type=None, pop=False,
+                augmenter=aug, encoder_lambda=0, aug_mix=0.0, discrete=False, random_process=None,
+                noise_clip=None, per=False, update_priorities=False, dr3_coeff=0.0)
+            for rd in dicts:
+                private = sorted(k_ for k_ in rd if isinstance(k_, str) and k_.startswith("_"))
+                assert set(private) <= {"_ssac", "_subset", "_x1"}, (setting, k, private)
+                hung = [n_ for n_ in vars(rd["td_target"]) if n_.startswith("_ssac")]
+                assert not hung, (setting, k, hung)
+        if recorded:
+            assert agent.__dict__.get("_ssac_fast"), "the fast C step was never reached"
+    finally:
+        L.USE_GRAPHS, L.LAUNCH_MODE, L.DUAL_LAUNCH, L.RANK1_BWD, L.FOLD_LOSS = old
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_late_bound_polyak_equals_the_polyak_launch(precision):
     """soft_update right behind a recorded critic update leaves a request in the input ring's tail and the update's own
