@@ -23,6 +23,7 @@ import torch
 
 import case_runner
 import synth
+from bf16_cases import unfrag   # (the one copy of the fragment-major formula under tests/)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,12 +56,6 @@ def test_shadow_layout_and_sync(in_dim, hidden, out_dim):
     assert stride % 8 == 0 and stride >= offs[3] + out_dim * hidden and ar.shadow.numel() == 3 * stride
     torch.cuda.synchronize()
 
-    def unfrag(flat, n_rows, n_cols):
-        """fragment-major -> row-major: element (n, k) lives at (((n // 32) * steps + k // 16) * 64 + n % 32 +
-        32 * (k // 8 % 2)) * 8 + k % 8 -- K-step t of a 32-row block is one contiguous KiB (csrc/ssac_bf16.hip)"""
-        steps = n_cols // 16
-        t = flat.view(n_rows // 32, steps, 2, 32, 8)            # [row block][K step][half][row in block][8 k]
-        return t.permute(0, 3, 1, 2, 4).reshape(n_rows, n_cols)  # -> [block, row, step, half, k]
     for j in range(3):
         sh = ar.shadow[j * stride:(j + 1) * stride]
         w1 = unfrag(sh[:hidden * k1p], hidden, k1p)
