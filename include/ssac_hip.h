@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 9
+#define SSAC_ABI_VERSION 10
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -687,6 +687,31 @@ typedef struct ssac_aug_op {
 } ssac_aug_op;
 int ssac_aug_chain(const void *src, int src_dtype, const int64_t *idx, int n, int c, int h, int w,
                    const ssac_aug_op *ops, int ops_stride, int n_ops, int n_aug, float *dst, void *stream);
+
+/* ---- Colour augmentations (csrc/ssac_aug_colour.hip): ColorJitterAug (augmentations.py:537-771) and
+ * NetworkRandomizationAug (augmentations.py:774-801).  Neither is an index map or a fill, so each has a kernel of its own
+ * beside ssac_aug_chain, with the same contract: src uint8 or fp32 (n x c x h x w) gathered through idx (may be NULL);
+ * dst fp32 (n x c x h x w), must not alias src; rows >= n_aug are a plain gather + convert (no round trip through 255).
+ * One workgroup handles one (row, group of three channels); the three source planes are staged in LDS in the source's type,
+ * so 3 * h * w * (1 or 4) bytes must not exceed SSAC_AUG_COLOUR_LDS_BYTES, and c / 3 <= SSAC_AUG_COLOUR_MAX_GROUPS.
+ * Channels beyond 3 * (c / 3) of an augmented row make the reference's x / 255 * 255 round trip in fp32 and nothing else.
+ *
+ * ssac_aug_colour_jitter: factors (n x 4 floats, device) = contrast, hue, brightness, saturation of row b (NOT of idx[b]).
+ *   Per group g, on x / 255:  contrast = clamp((x - mean) * fc + mean, 0, 1), mean over (h, w) per image and channel;
+ *   HSV block = rgb2hsv (eps 1e-8; hue by Cmax == r, then == g, then == b, so b wins ties over g over r; floor-mod 6 on the
+ *   r branch only; hue = sat = 0 where Cmax == 0), v = clamp(v * fb), h = (h + (fh * 255) / 360) floor-mod 1,
+ *   s = clamp(s * fs), hsv2rgb (six half-open sectors of hue * 360; a hue of exactly 360 matches none and gives (m, m, m)),
+ *   clamp.  Bit g of contrast_first set: contrast, then the HSV block; clear: the HSV block, then contrast (the mean is then
+ *   taken over the HSV block's output).  The result is multiplied by 255.  fp32 throughout, in the reference's operation
+ *   order; the plane sums are reduced in a fixed order (no atomics), so two launches are bit-equal.
+ * ssac_aug_netrand: weight (81 floats, device) = [co][ci][ky][kx] of Conv2d(3, 3, 3, bias=False, padding=1), one for every
+ *   row: zero-padded 3 x 3 cross-correlation of x / 255 on every group (27 taps per output), times 255, no clamp. */
+#define SSAC_AUG_COLOUR_LDS_BYTES (96 * 1024)
+#define SSAC_AUG_COLOUR_MAX_GROUPS 32
+int ssac_aug_colour_jitter(const void *src, int src_dtype, const int64_t *idx, int n, int c, int h, int w,
+                           const float *factors, uint32_t contrast_first, int n_aug, float *dst, void *stream);
+int ssac_aug_netrand(const void *src, int src_dtype, const int64_t *idx, int n, int c, int h, int w,
+                     const float *weight, int n_aug, float *dst, void *stream);
 
 /* ==== fused kernels (csrc/ssac_fused.hip): the same arithmetic as the per-layer entry points above,
  * with the activations of a 32-row tile kept in LDS across fc1 -> fc2 -> head.  Supported when

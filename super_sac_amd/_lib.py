@@ -180,6 +180,8 @@ SIGNATURES = {
     "ssac_ensemble_min_select": [_P, _I, _I, _I, _P, _L, _P, _P],
     "ssac_drq_shift": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P],
     "ssac_aug_chain": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
+    "ssac_aug_colour_jitter": [_P, _I, _P, _I, _I, _I, _I, _P, C.c_uint32, _I, _P, _P],
+    "ssac_aug_netrand": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P],
     "ssac_zero": [_P, _L, _P],
     "ssac_im2col": [_P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P],
     "ssac_col2im": [_P, _P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P],
@@ -296,7 +298,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def _load():

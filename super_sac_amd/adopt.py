@@ -19,8 +19,9 @@ Nothing is copied: weights stay in the torch modules' (re-pointed) parameters, s
 The other two objects the training scripts build with the reference's classes are adopted the same way, in place:
 
   augmenter         a reference ``AugmentationSequence`` (augmentations.py:20-41) whose ``aug_list`` holds DrQ-family,
-                    cutout / translate / flip / rotate / window / gamma or identity augmentations (matched by class NAME
-                    along the MRO, and by the state that class keeps): every element and the sequence itself change
+                    cutout / translate / flip / rotate / window / gamma, colour-jitter / network-randomisation or identity
+                    augmentations (matched by class NAME along the MRO, and by the state that class keeps; a colour-jitter
+                    object also by the settings the reference itself can run): every element and the sequence itself change
                     class to this package's; batch size, parameters and the CURRENT randomisation (``shift`` / ``w1, h1``
                     / ``translation`` ...) are kept, no host draw is consumed
   buffer            a reference ``ReplayBuffer`` (replay.py:140-190: numpy ``ReplayBufferStorage`` + float64 segment
@@ -110,7 +111,7 @@ def probe_identity(encoder, obs_dict):
 # ------------------------------------------------------------------------------------------ augmenters
 _AUG_NAMES = ("Drqv2Aug", "DrqNoNoiseAug", "LargeDrqNoNoiseAug", "LargeDrqAug", "DrqAug", "IdentityAug",
               "CutoutAug", "CutoutColorAug", "LargeTranslateAug", "TranslateAug", "HorizontalFlipAug", "VerticalFlipAug",
-              "RotateAug", "WindowAug", "GammaAug")
+              "RotateAug", "WindowAug", "GammaAug", "ColorJitterAug", "NetworkRandomizationAug")
 
 # the reference's augmentations this engine refuses, and why
 _AUG_REFUSED = {
@@ -118,10 +119,16 @@ _AUG_REFUSED = {
                     "1 or 3 rows are selected and is not a per-image grayscale when it does run: there is nothing to be on "
                     "parity with",
     "RadAug": "it resizes with cv2.resize (augmentations.py:129-162), and no reference output exists to match without it",
-    "ColorJitterAug": "it draws inside forward() and on the device generator and needs per-image reductions "
-                      "(augmentations.py:537-690); not built yet",
-    "NetworkRandomizationAug": "it draws a fresh convolution on the device generator per randomisation and applies it "
-                               "(augmentations.py:774-801); not built yet",
+}
+
+
+# what an object that has only the NAME of one of these two lacks (the general wording serves every other class)
+_AUG_STATE_NOTE = {
+    "ColorJitterAug": "it is named like the reference's ColorJitterAug, which keeps four per-row factor vectors and draws "
+                      "inside forward() (row selection and transform order, per application: augmentations.py:627, 681), "
+                      "but does not carry its state",
+    "NetworkRandomizationAug": "it is named like the reference's NetworkRandomizationAug but does not carry the convolution "
+                               "the reference's change_randomization_params() leaves",
 }
 
 
@@ -151,18 +158,21 @@ def adopt_augmenter(augmenter):
         raise TypeError(f"{type(augmenter).__name__}: expected an AugmentationSequence (augmentations.py:20-41)")
     swaps = []
     for aug in aug_list:
-        if isinstance(aug, (A._ShiftAug, A._ChainAug, A.IdentityAug)):
+        if isinstance(aug, (A._ShiftAug, A._ChainAug, A._ColourAug, A.IdentityAug)):
             swaps.append(None)
             continue
         mine = _own_aug_class(aug)
         if mine is None:
             raise NotImplementedError(_refusal(aug))
         # the NAME alone does not make it the reference's class: it has to carry that class's state
-        missing = [n for n in ("batch_size",) + tuple(getattr(mine, "REF_STATE", ())) if not hasattr(aug, n)]
+        need = (("batch_size",) if getattr(mine, "NEEDS_BATCH_SIZE", True) else ()) + tuple(getattr(mine, "REF_STATE", ()))
+        missing = [n for n in need if not hasattr(aug, n)]
         if missing:
-            raise NotImplementedError(
-                f"augmentation {type(aug).__name__!r} has no HIP path: it is named like the reference's {mine.__name__} "
-                f"but does not carry its state (missing {missing})")
+            note = _AUG_STATE_NOTE.get(mine.__name__, f"it is named like the reference's {mine.__name__} but does not carry "
+                                                      "its state")
+            raise NotImplementedError(f"augmentation {type(aug).__name__!r} has no HIP path: {note} (missing {missing})")
+        if mine is A.ColorJitterAug and A.jitter_refusal(aug):
+            raise NotImplementedError(f"augmentation {type(aug).__name__!r} has no HIP path for {A.jitter_refusal(aug)}")
         swaps.append(mine)
     for aug, mine in zip(aug_list, swaps):
         if mine is None:

@@ -4,11 +4,18 @@ shared by every batch passed (s and s' get the same shift / box / flip ...).
 DrQ family (augmentations.py:165-293): the ``ssac_drq_shift`` kernel.  Cutout, cutout-color, translate, flips,
 rotate, window and gamma (augmentations.py:83-126, 296-534): the ``ssac_aug_chain`` kernel, which evaluates a
 whole sequence of them in one pass (a per-row op table, built on the host from the reference's draws and uploaded
-once per randomisation).  When used through ``learning_utils.sample_move_and_augment`` both kernels read the uint8
-replay rows directly (gather + uint8->fp32 + augmentation + aug_mix row selection fused, one pass over the pixels).
+once per randomisation).  Colour jitter and network randomisation (augmentations.py:537-801) are neither an index map nor a
+fill: each is a device pass of its own (``ssac_aug_colour_jitter``, ``ssac_aug_netrand``; one workgroup per row and group of
+three channels).  When used through ``learning_utils.sample_move_and_augment`` every kernel reads the uint8 replay rows
+directly (gather + uint8->fp32 + augmentation + aug_mix row selection fused, one pass over the pixels).
 
-Not covered (``adopt.adopt_augmenter`` says why): GrayscaleAug, RadAug, ColorJitterAug, NetworkRandomizationAug.
+ColorJitterAug also draws at APPLICATION time (the row selection and the contrast / HSV order, per frame group): a sequence
+that holds one draws the orders of a whole call up front, in the reference's order (``AugmentationSequence.draw_orders``).
+
+Not covered (``adopt.adopt_augmenter`` says why): GrayscaleAug, RadAug.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -211,8 +218,9 @@ class _ChainPlan:
 
 class _DevicePasses:
     """a sequence as device passes: one ssac_aug_chain launch per run of chain augmentations, one ssac_drq_shift launch
-    per DrQ-family member.  The first pass reads the source (replay rows through idx), later ones a temporary -- an
-    index map cannot run in place.  A DrQ member that adds noise is refused in a mixed sequence: its N(0, 1) draws come from
+    per DrQ-family member, one ssac_aug_colour_jitter / ssac_aug_netrand launch per colour member.  The first pass reads the
+    source (replay rows through idx), later ones a temporary -- an index map cannot run in place.  A DrQ member that adds
+    noise is refused in a mixed sequence: its N(0, 1) draws come from
     the device generator, and no recorded reference output pins how they interleave with the other members' passes."""
 
     def __init__(self, aug_list):
@@ -232,13 +240,19 @@ class _DevicePasses:
         if run:
             self.passes.append(_ChainPlan(run))
 
-    def run(self, src, idx, n, c, h, w, n_aug, device):
+    def run(self, src, idx, n, c, h, w, n_aug, device, orders=None):
+        """orders: the contrast-first bit masks of this application, one per ColorJitterAug pass in pass order
+        (AugmentationSequence.draw_orders); None: each such pass draws its own now, as a stand-alone call does"""
         cur, cur_idx = src, idx
+        jitters = 0
         for p in self.passes:
             out = torch.empty(n, c, h, w, device=device, dtype=torch.float32)
             if isinstance(p, _ShiftAug):
                 assert h == w
                 p.apply(cur, cur_idx, n, c, h, n_aug, out, None)
+            elif isinstance(p, ColorJitterAug):
+                p.apply(cur, cur_idx, n, c, h, w, n_aug, out, None if orders is None else orders[jitters])
+                jitters += 1
             else:
                 p.apply(cur, cur_idx, n, c, h, w, n_aug, out)
             cur, cur_idx = out, None
@@ -452,6 +466,193 @@ class GammaAug(_ChainAug):
         return "Gamma"
 
 
+# ------------------------------------------------------------------------------------------ colour augmentations
+class _ColourAug:
+    """an augmentation with a kernel of its own that works on groups of three channels (csrc/ssac_aug_colour.hip): a device
+    pass of its own kind in _DevicePasses.  The randomisation lives in the attributes the reference's class of the same name
+    keeps (REF_STATE); its device copy is uploaded once per randomisation and kept until the state changes -- through
+    change_randomization_params() / _adopt_state(), or by ASSIGNING a new object to a REF_STATE attribute.  Writing INTO such
+    a tensor in place is not seen; call _bump() after it."""
+    REF_STATE = ()
+    NEEDS_BATCH_SIZE = True   # (adopt.adopt_augmenter: the reference's object carries `batch_size`)
+
+    _state_key = _ChainAug._state_key
+    _bump = _ChainAug._bump
+
+    def _adopt_state(self):
+        self._bump()
+
+    def _host_params(self):
+        """the float32 tensor the kernel reads"""
+        raise NotImplementedError
+
+    def _device_params(self, device):
+        key = (self._state_key(), device)
+        if key != self.__dict__.get("_dev_key"):
+            # (the state objects the key names are held while it is current, so their ids cannot be reused meanwhile)
+            self._held = [self.__dict__.get(n) for n in self.REF_STATE]
+            self._dev, self._dev_key = self._host_params().contiguous().to(device), key
+        return self._dev
+
+
+def _jitter_range(setting, name, around, floor=None, inside=(None, None)):
+    """the [lo, hi] interval a ColorJitterAug factor is drawn from, or None where the interval is the single point `around`
+    (the factor would change nothing).  A scalar s stands for [around - s, around + s], its lower end cut off at `floor`
+    where one is given; a pair is used as it is and has to lie within `inside`."""
+    if isinstance(setting, numbers.Real):
+        if setting < 0:
+            raise ValueError(f"ColorJitterAug: {name}={setting!r} is a half-width and cannot be negative")
+        lo, hi = around - setting, around + setting
+        interval = [lo if floor is None else max(lo, floor), hi]
+    else:
+        try:
+            lo, hi = setting
+        except (TypeError, ValueError):
+            raise TypeError(f"ColorJitterAug: {name} takes a half-width or a (lo, hi) pair, not {setting!r}") from None
+        least, most = inside
+        if not (lo <= hi and (least is None or least <= lo) and (most is None or hi <= most)):
+            raise ValueError(f"ColorJitterAug: {name}={setting!r} is not an interval within {inside}")
+        interval = setting
+    return None if interval[0] == interval[1] == around else interval
+
+
+def jitter_refusal(aug):
+    """why the reference's own ColorJitterAug fails with this object's settings (None: it runs)"""
+    if aug.stack_size != 1:
+        return (f"stack_size = {aug.stack_size}: the reference's own class raises for every stack_size but 1 "
+                "(factor.view(len(x), 1, 1, 1) of a batch_size * stack_size vector, augmentations.py:594)")
+    if aug.prob != 1.0:
+        return (f"p_rand = {aug.prob}: the reference's own class raises whenever a row is left out (the same view, taken on "
+                "the selected rows only, augmentations.py:594-686), so only p_rand = 1.0 has an output to match")
+    for name in ("contrast", "hue", "brightness", "saturation"):
+        if getattr(aug, name) is None:
+            return (f"{name} is a zero range (None): the reference's own class raises in uniform_(*None) "
+                    "(augmentations.py:648-675)")
+    return None
+
+
+class ColorJitterAug(_ColourAug):
+    """per-row contrast, hue, brightness and saturation factors on every group of three channels (augmentations.py:537-771):
+    x / 255, then contrast = clamp((x - mean) * fc + mean) with the mean over (H, W) per image and channel and the HSV block
+    (rgb2hsv, brightness, hue, saturation, hsv2rgb) in an order that is drawn PER APPLICATION AND FRAME GROUP
+    (rng.draw_jitter_order), then * 255.  Channels beyond 3 * (c // 3) only make the / 255 * 255 round trip.  The quirks of
+    the reference's formulas that the kernel keeps are listed in include/ssac_hip.h (ssac_aug_colour_jitter).
+
+    Only what the reference itself can run is accepted: stack_size == 1, p_rand == 1.0 and four non-zero ranges
+    (jitter_refusal)."""
+    REF_STATE = ("brightness", "contrast", "saturation", "hue", "prob", "stack_size",
+                 "factor_contrast", "factor_hue", "factor_brightness", "factor_saturate")
+    MAX_GROUPS = 32   # SSAC_AUG_COLOUR_MAX_GROUPS: one bit per frame group
+
+    def __init__(self, batch_size, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.5, p_rand=1.0, stack_size=1,
+                 *_a, **_k):
+        self.brightness = _jitter_range(brightness, "brightness", 1, floor=0, inside=(0, None))
+        self.contrast = _jitter_range(contrast, "contrast", 1, floor=0, inside=(0, None))
+        self.saturation = _jitter_range(saturation, "saturation", 1, floor=0, inside=(0, None))
+        self.hue = _jitter_range(hue, "hue", 0, inside=(-0.5, 0.5))
+        self.prob = p_rand
+        self.batch_size = batch_size
+        self.stack_size = stack_size
+        why = jitter_refusal(self)
+        if why:
+            raise NotImplementedError(f"augmentation 'ColorJitterAug' has no HIP path for {why}")
+        self.change_randomization_params()
+
+    def change_randomization_params(self):
+        (self.factor_contrast, self.factor_hue, self.factor_brightness,
+         self.factor_saturate) = rng.draw_color_jitter(self.batch_size, self.contrast, self.hue, self.brightness,
+                                                       self.saturation)
+        self._bump()
+
+    def _adopt_state(self):
+        why = jitter_refusal(self)
+        if why:
+            raise NotImplementedError(f"augmentation 'ColorJitterAug' has no HIP path for {why}")
+        self._bump()
+
+    def _host_params(self):
+        cols = [torch.as_tensor(getattr(self, n)).detach().cpu().float().reshape(self.batch_size)
+                for n in ("factor_contrast", "factor_hue", "factor_brightness", "factor_saturate")]
+        return torch.stack(cols, dim=1)   # (B, 4): contrast, hue, brightness, saturation
+
+    def draw_order(self, c):
+        """the draws of ONE application to a c-channel batch: bit g set = group g applies contrast before the HSV block"""
+        groups = c // 3
+        if groups > self.MAX_GROUPS:
+            raise RuntimeError(f"{self!r}: {groups} groups of three channels, ssac_aug_colour_jitter takes {self.MAX_GROUPS}")
+        bits = 0
+        for g in range(groups):
+            if rng.draw_jitter_order(self.batch_size, self.prob):
+                bits |= 1 << g
+        return bits
+
+    def apply(self, src, idx, n, c, h, w, n_aug, dst, order=None):
+        assert n == self.batch_size, "the randomisation was drawn for `batch_size` rows"
+        assert src.dtype in (torch.uint8, torch.float32) and dst.dtype == torch.float32
+        if order is None:
+            order = self.draw_order(c)
+        check(lib.ssac_aug_colour_jitter(src.data_ptr(), 1 if src.dtype == torch.uint8 else 0,
+                                         0 if idx is None else idx.data_ptr(), n, c, h, w,
+                                         self._device_params(dst.device).data_ptr(), order, n_aug, dst.data_ptr(),
+                                         engine.stream()))
+        return dst
+
+    def __call__(self, imgs):
+        engine.require_gpu(imgs)
+        n, c, h, w = imgs.shape
+        return self.apply(imgs.contiguous(), None, n, c, h, w, n,
+                          torch.empty(n, c, h, w, device=imgs.device, dtype=torch.float32))
+
+    def __repr__(self):
+        return "ColorJitter"
+
+
+def _conv_holding(weight):
+    """a Conv2d(3, 3, 3, bias=False, padding=1) around `weight` (what the reference keeps as ``conv``), built without
+    touching any generator"""
+    conv = torch.nn.utils.skip_init(torch.nn.Conv2d, 3, 3, kernel_size=3, bias=False, padding=1)
+    conv.weight.data = torch.as_tensor(weight).detach().float().reshape(3, 3, 3, 3)
+    return conv
+
+
+class NetworkRandomizationAug(_ColourAug):
+    """one random Conv2d(3, 3, 3, bias=False, padding=1) per randomisation, the same for every row, on every group of three
+    channels of x / 255; times 255, NOT clamped -- outputs leave [0, 255], as the reference's do (augmentations.py:774-801).
+    Like the reference's object it keeps ``conv`` and nothing else: no batch size."""
+    REF_STATE = ("conv",)
+    NEEDS_BATCH_SIZE = False
+
+    def __init__(self, batch_size=None, *_a, **_k):
+        self.change_randomization_params()
+
+    def change_randomization_params(self):
+        self.conv = _conv_holding(rng.draw_netrand_conv())
+        self._bump()
+
+    def _adopt_state(self):
+        # (an object built by the reference's class is a torch.nn.Module: it keeps `conv` among its sub-modules)
+        mods = self.__dict__.get("_modules")
+        if "conv" not in self.__dict__ and mods and "conv" in mods:
+            self.__dict__["conv"] = mods["conv"]
+        self._bump()
+
+    def _host_params(self):
+        return self.conv.weight.detach().cpu().float().reshape(81)   # [co][ci][ky][kx]
+
+    def apply(self, src, idx, n, c, h, w, n_aug, dst):
+        assert src.dtype in (torch.uint8, torch.float32) and dst.dtype == torch.float32
+        check(lib.ssac_aug_netrand(src.data_ptr(), 1 if src.dtype == torch.uint8 else 0,
+                                   0 if idx is None else idx.data_ptr(), n, c, h, w,
+                                   self._device_params(dst.device).data_ptr(), n_aug, dst.data_ptr(), engine.stream()))
+        return dst
+
+    def __call__(self, imgs):
+        engine.require_gpu(imgs)
+        n, c, h, w = imgs.shape
+        return self.apply(imgs.contiguous(), None, n, c, h, w, n,
+                          torch.empty(n, c, h, w, device=imgs.device, dtype=torch.float32))
+
+
 class AugmentationSequence:
     def __init__(self, aug_list, keys=None):
         self.aug_list = aug_list
@@ -477,10 +678,11 @@ class AugmentationSequence:
         return None
 
     def device_passes(self):
-        """the sequence as device passes (_DevicePasses) when it holds a chain augmentation and every non-identity member
-        has a kernel, else None.  Cached while the members stay the same objects."""
+        """the sequence as device passes (_DevicePasses) when it holds a chain or colour augmentation and every non-identity
+        member has a kernel, else None.  Cached while the members stay the same objects."""
         real = self._real()
-        if not any(isinstance(a, _ChainAug) for a in real) or not all(isinstance(a, (_ChainAug, _ShiftAug)) for a in real):
+        if (not any(isinstance(a, (_ChainAug, _ColourAug)) for a in real)
+                or not all(isinstance(a, (_ChainAug, _ShiftAug, _ColourAug)) for a in real)):
             return None
         cached = self.__dict__.get("_passes")
         if cached is None or len(cached[0]) != len(real) or any(a is not b for a, b in zip(cached[0], real)):
@@ -491,7 +693,26 @@ class AugmentationSequence:
         for aug in self.aug_list:
             aug.change_randomization_params()
 
-    def _augment_one(self, batch):
+    def draw_orders(self, *channels):
+        """the APPLICATION-time draws of one call, made up front: ColorJitterAug draws its row selection and its contrast /
+        HSV order per application and per frame group (rng.draw_jitter_order), and the reference consumes those draws
+        batch-major (s, then s'), then key in ``self.keys`` order, then member, then frame group (augmentations.py:31-36).
+        `channels`: one {key: channel count} dict per batch, its 4-D (image) keys.  Returns None when no member draws at
+        application time, else one {key: (bit mask per ColorJitterAug member)} dict per batch; a key outside ``self.keys``
+        is not augmented and draws nothing (masks of 0).  Needs no GPU."""
+        jitters = [a for a in self.aug_list if isinstance(a, ColorJitterAug)]
+        if not jitters:
+            return None
+        out = []
+        for chan in channels:
+            keys = list(chan) if self.keys is None else [k for k in self.keys if k in chan]
+            per_key = {k: (0,) * len(jitters) for k in chan}
+            for k in keys:
+                per_key[k] = tuple(j.draw_order(chan[k]) for j in jitters)
+            out.append(per_key)
+        return out
+
+    def _augment_one(self, batch, orders=None):
         """one observation dict through every augmentation, key by key; keys outside `self.keys` pass through as copies"""
         out = {}
         passes = self.device_passes()
@@ -499,7 +720,8 @@ class AugmentationSequence:
             if name in self.keys and passes is not None and value.dim() == 4:
                 engine.require_gpu(value)
                 n, c, h, w = value.shape
-                value = passes.run(value.contiguous(), None, n, c, h, w, n, value.device)
+                value = passes.run(value.contiguous(), None, n, c, h, w, n, value.device,
+                                   None if orders is None else orders[name])
             else:
                 value = value.clone()
                 if name in self.keys:
@@ -514,7 +736,10 @@ class AugmentationSequence:
         if self.keys is None:   # (first call: every key of the first batch, remembered -- as the reference does)
             self.keys = batches[0].keys()
         self.change_randomization_params()
-        augmented = tuple(self._augment_one(b) for b in batches)
+        orders = None
+        if self.device_passes() is not None:
+            orders = self.draw_orders(*({k: v.shape[1] for k, v in b.items() if v.dim() == 4} for b in batches))
+        augmented = tuple(self._augment_one(b, None if orders is None else orders[i]) for i, b in enumerate(batches))
         return augmented[0] if len(augmented) == 1 else augmented
 
     def __repr__(self):

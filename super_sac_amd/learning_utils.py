@@ -348,6 +348,13 @@ def _host_view(idx):
     return idx.numpy() if torch.is_tensor(idx) else idx
 
 
+def draw_augmentation_orders(augmenter, channels):
+    """the application-time draws of one sample_move_and_augment call (AugmentationSequence.draw_orders): s, then s', each
+    over the image keys `channels` ({key: channel count}) in the augmenter's key order.  None when the augmenter holds no
+    member that draws at application time.  Needs no GPU."""
+    return augmenter.draw_orders(channels, channels)
+
+
 def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _defer_gather=False,
                             _invariance=False):
     assert len(buffer) >= batch_size
@@ -374,6 +381,9 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
     d = torch.empty(B, 1, device=dev)
     # one randomisation per call, shared by s and s' (augmentations.py:28-29)
     augmenter.change_randomization_params()
+    # ... and the application-time draws of the whole call (ColorJitterAug), before any key is augmented: the loop below
+    # walks key-major, the reference's augmenter(oo, oo1) batch-major
+    orders = draw_augmentation_orders(augmenter, {k: v.shape[1] for k, v in st.s_stack.items() if v.dim() == 4})
     bt = _Batch()
     bt.B, bt.A, bt.pending = B, A, None
     vec = len(keys) == 1 and st.s_stack[keys[0]].dim() == 2
@@ -419,8 +429,8 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
                 # (a key outside AugmentationSequence.keys is left alone, augmentations.py:33: gather + convert only)
                 listed = augmenter.keys is None or key in augmenter.keys
                 k_key = k_aug if listed else 0
-                o[key] = passes.run(src, idx, B, c, h, w, k_key, dev)
-                o1[key] = passes.run(src1, idx, B, c, h, w, k_key, dev)
+                o[key] = passes.run(src, idx, B, c, h, w, k_key, dev, orders and orders[0][key])
+                o1[key] = passes.run(src1, idx, B, c, h, w, k_key, dev, orders and orders[1][key])
             else:
                 assert augmenter.is_identity(), "unsupported augmentation on the accelerated path"
                 o[key] = st.gather_field(src, idx, B)
@@ -453,7 +463,9 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
                     listed = augmenter.keys is None or key in augmenter.keys
                     k_key = k_aug if listed else 0
                     for dst_dict, n_aug in ((ao, B if listed else 0), (oo, 0)):
-                        dst_dict[key] = o[key] if n_aug == k_key else passes.run(src, idx, B, c, h, w, n_aug, dev)
+                        # (the same rows under the same randomisation: the order flags of (s, key) again, nothing drawn)
+                        dst_dict[key] = o[key] if n_aug == k_key else passes.run(src, idx, B, c, h, w, n_aug, dev,
+                                                                                 orders and orders[0][key])
                 else:
                     ao[key] = oo[key] = o[key]
             inv_obs = ((ao, None), (oo, None))

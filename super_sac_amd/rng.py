@@ -5,6 +5,10 @@ so a run that swaps in this engine consumes them identically (SURVEY.md section 
   cutout / translate / rotate /   torch CPU default generator   (augmentations.py:99, 311, 386, 477, 526)
   window parameters
   flip rows, gamma exponents      numpy's global generator      (augmentations.py:412, 441)
+  colour-jitter factors,          torch CPU default generator   (augmentations.py:648-675, 794-798; the reference draws
+  network-randomisation conv                                     these on the CUDA generator where CUDA is present)
+  colour-jitter rows and order    numpy's global generator, then Python ``random`` (augmentations.py:627, 681), per
+                                  application and frame group
   REDQ target subset, logged net  Python ``random``             (agent.py:29, learning.py:135)
   action noise eps                generator of the compute device (distributions: Normal.sample)
   Beta policy draws x             the agent's engine Philox stream, inside ssac_beta_fwd (beta_dist=True)
@@ -134,3 +138,33 @@ def draw_window(batch_size, crop_max):
 def draw_gamma(batch_size, mean, std):
     """GammaAug (augmentations.py:411-415): numpy's global generator, cast to float32, shaped (B, 1, 1, 1)"""
     return torch.from_numpy(np.random.normal(mean, std, size=(batch_size,))).float().view(-1, 1, 1, 1)
+
+
+# ---- colour augmentations (augmentations.py:537-801)
+def draw_color_jitter(batch_size, contrast, hue, brightness, saturation):
+    """ColorJitterAug.change_randomization_params (augmentations.py:648-675): four ``torch.empty(B).uniform_(lo, hi)``
+    vectors in the reference's order -- contrast, hue, brightness, saturation -- on torch's CPU generator.  That is where the
+    reference draws them on a machine without CUDA (its ``_device`` is then the CPU); with CUDA it uses the device
+    generator.  The fixtures under tests/golden were recorded on the CPU, and a run that swaps in this engine keeps the CPU
+    stream on every machine."""
+    return tuple(torch.empty(batch_size).uniform_(*r) for r in (contrast, hue, brightness, saturation))
+
+
+def draw_jitter_order(batch_size, prob):
+    """ColorJitterAug.forward + transform (augmentations.py:627, 681-686), ONE application to ONE group of three channels:
+    the row selection from numpy's global generator (consumed even at prob == 1), then -- if any row was picked --
+    ``random.uniform(0, 1) >= 0.5`` from Python's generator.  True: contrast first, then the HSV block; False: the HSV block
+    first.  These are draws per application and per frame group, not per randomisation."""
+    picked = np.random.choice([True, False], batch_size, p=[prob, 1 - prob])
+    if picked.sum() > 0:
+        return random.uniform(0, 1) >= 0.5
+    return False
+
+
+def draw_netrand_conv():
+    """NetworkRandomizationAug.change_randomization_params (augmentations.py:794-798): ``Conv2d(3, 3, 3, bias=False,
+    padding=1)`` -- its default initialisation consumes torch's CPU generator -- then ``xavier_normal_`` on the weight, as
+    the reference does where its ``_device`` is the CPU.  Returns the (3, 3, 3, 3) weight [co][ci][ky][kx]."""
+    conv = torch.nn.Conv2d(3, 3, kernel_size=3, bias=False, padding=1)
+    torch.nn.init.xavier_normal_(conv.weight.data)
+    return conv.weight.data

@@ -1,10 +1,13 @@
-"""Time ssac_aug_chain against the DrQv2 mode of ssac_drq_shift on the MI355X (profiles/aug_chain.md).
+"""Time ssac_aug_chain, ssac_aug_colour_jitter and ssac_aug_netrand against the DrQv2 mode of ssac_drq_shift on the MI355X
+(profiles/aug_chain.md).
 
     python tools/bench_aug.py [--batch 512] [--regions 15] [--launches 50]
 
 Shape: B x 9 x 84 x 84, uint8 replay rows read through idx, fp32 out -- what one observation batch of the DMC pixel
 configuration moves.  The kernels alternate region by region in one process (warm clocks, same machine state): a single
-TranslateAug, the four-member chain [Rotate, Window, Gamma, Cutout] (also without its gamma, and the gamma alone), and Drqv2Aug.  A region is `launches` back-to-back
+TranslateAug, the four-member chain [Rotate, Window, Gamma, Cutout] (also without its gamma, and the gamma alone), ColorJitterAug
+alone (both orders among its three frame groups), NetworkRandomizationAug alone, the three passes of [Translate, ColorJitter,
+HorizontalFlip] (the figure of that row is all three launches and its two fp32 temporaries), and Drqv2Aug.  A region is `launches` back-to-back
 launches between two device events; the figure of a kernel is the median over its regions, with min and max as the spread.
 Bytes per launch = B * 9 * 84 * 84 * (1 read + 4 written).
 """
@@ -42,6 +45,11 @@ def main():
     }
     shift = A.Drqv2Aug(B)
     runs = {name: (lambda p=p: p.apply(src, idx, B, c, h, h, B, out)) for name, p in plans.items()}
+    jitter, netrand = A.ColorJitterAug(B), A.NetworkRandomizationAug(B)
+    mixed = A._DevicePasses([A.TranslateAug(B), A.ColorJitterAug(B), A.HorizontalFlipAug(B)])
+    runs["colour_jitter"] = lambda: jitter.apply(src, idx, B, c, h, h, B, out, 0b101)
+    runs["netrand"] = lambda: netrand.apply(src, idx, B, c, h, h, B, out)
+    runs["translate_jitter_hflip"] = lambda: mixed.run(src, idx, B, c, h, h, B, dev, (0b101,))
     runs["drqv2_shift"] = lambda: shift.apply(src, idx, B, c, h, B, out)
     for fn in runs.values():                        # warm-up: code objects, table uploads, clocks
         for _ in range(200):
@@ -63,7 +71,8 @@ def main():
         med = statistics.median(ts)
         res[name] = {"median_us": round(med, 2), "min_us": round(min(ts), 2), "max_us": round(max(ts), 2),
                      "gb_per_s": round(nbytes / med / 1e3, 1)}
-    for name in plans:
+    for name in [n for n in runs if n != "drqv2_shift"]:
+        res[name]["ratio_to_translate"] = round(res[name]["median_us"] / res["translate"]["median_us"], 3)
         res[name]["ratio_to_drqv2_shift"] = round(res[name]["median_us"] / res["drqv2_shift"]["median_us"], 3)
     print(json.dumps(res))
 
