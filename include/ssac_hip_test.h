@@ -51,6 +51,12 @@ int ssac_xcd_order(int mask);
  * slower, profiles/r5_chain_coresident.md).  Outputs are bit-identical to the 16-row tiles of the one-per-CU form
  * (ssac_fused_tile_rows(16)); against its 32-row tiles they differ by fp32 association of the K sums. */
 int ssac_chain_form(int form);
+/* default 1: the critic tiles of the producer / consumer launch (ssac_chain_update with a hand-off buffer) run their lean
+ * instantiation -- hidden 256, one head output, an input of at most 32 columns, 32-row tiles, a double-buffered actor --
+ * whenever the launch qualifies; 0 = always the general instantiation.  Bit-identical results. */
+int ssac_chain_lean(int on);
+/* which of the two the LAST ssac_chain_update launch took: 1 lean, 0 general, -1 no launch yet. */
+int ssac_chain_lean_taken(void);
 /* large-batch form of ssac_bf16_mlp3_fwd: 1 (default) = the register-chained kernel where it applies, 0 = the streaming
  * kernel everywhere.  Same operands, same rounding points. */
 int ssac_bf16_fwd_form(int form);

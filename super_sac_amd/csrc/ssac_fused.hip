@@ -751,16 +751,25 @@ __device__ __forceinline__ void stage_head_weights(float *w3s, const float *__re
 // fused_chain_co_kernel) -- 16-row tiles; h2 / dz2u take h1's place in LDS (fc2's epilogue runs behind the K loop's closing
 // barrier, when nobody reads h1 any more), and the ReLU mask of h1 that the backward-data epilogue needs stays in a
 // register: a lane's accumulator elements are the same (row, column) set in fc1 and in the backward-data GEMM.
-template <int MODE, int TMR, bool DBUF, bool HO = false, bool W3LATE = false, bool CO = false>
+// LEAN (MODE_CRITIC_U, the chained launch's critic tiles; ssac_chain_update decides per launch): the instantiation
+// for hidden 256, ONE head output, an input of at most 32 columns (fc1 is a single K chunk) and no dQ/da -- H, OUT, the LDS
+// strides and the chunk counts are constants, and the wide-input loop, the ragged K tails, the matrix-core head, the
+// selector and the dQ/da tail are not compiled at all.  The one-shot phases of a tile (prologue, epilogues) run their code
+// exactly once, from cold instruction caches: what they do not need should not lie between them (headline: 52.3 ->
+// 50.7 us per update, all of it in this launch; profiles/chain_lean.md).  Same operations in the same order as the
+// general instantiation: bit-identical (tests/test_hip_chain_lean.py).
+template <int MODE, int TMR, bool DBUF, bool HO = false, bool W3LATE = false, bool CO = false, bool LEAN = false>
 __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, const int bx, const int e,
                                                const int grid_x, const int dbg_off = 0, const int split = 0) {
     static_assert(!W3LATE || (MODE == MODE_SAMPLE && DBUF), "the late head image is the actor pass's, behind a double-buffered fc2");
     static_assert(!CO || (TMR == 16 && !W3LATE && (MODE == MODE_PLAIN || MODE == MODE_SAMPLE || MODE == MODE_CRITIC_U)),
                   "the co-resident carve: 16-row tiles of the chained launch's three roles");
+    static_assert(!LEAN || (MODE == MODE_CRITIC_U && DBUF && !HO && !W3LATE && !CO), "the lean form is the chained launch's critic tile");
     typedef Tile<TMR> T;
-    const int H = g.hidden, IN = g.in_dim, OUT = g.out_dim;
-    const int ldo = (OUT + 15) & ~15;  // row stride of the per-row head outputs / output gradients in LDS
-    const int KP = (IN + 31) & ~31;
+    const int H = LEAN ? 256 : g.hidden, IN = g.in_dim, OUT = LEAN ? 1 : g.out_dim;
+    const int K1 = LEAN ? 32 : IN;   // fc1's K extent as the K loop sees it (LEAN: the one chunk, zero-padded behind IN)
+    const int ldo = LEAN ? 16 : (OUT + 15) & ~15;  // row stride of the per-row head outputs / output gradients in LDS
+    const int KP = LEAN ? 32 : (IN + 31) & ~31;
     const int ldx_s = KP + APAD, ldh = H + APAD;
     float *xs = smem;                       // [TMR][KP+4]
     float *h1s = xs + TMR * ldx_s;          // [TMR][H+4]
@@ -1098,9 +1107,9 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
                 rowin[tid] = ok ? td_of_row(g, b, e) : 0.0f;
                 rowin[TMR + tid] = (ok && g.weight) ? g.weight[b] : 1.0f;
             }
-            rowin[2 * TMR + tid] = (ok && OUT > 1) ? g.act[b * g.ld_a] : 0.0f;
+            if (!LEAN) rowin[2 * TMR + tid] = (ok && OUT > 1) ? g.act[b * g.ld_a] : 0.0f;   // (read by heads of OUT > 1 only)
         }
-        if constexpr (!CO) stage_first(st1, Ws, IN, tid);
+        if constexpr (!CO) stage_first(st1, Ws, K1, tid);
         // (every barrier of this body hands data over through LDS only, so it does not drain vmcnt: the activation
         // tiles written out for the weight-gradient launch, the gathered rows and the next phase's prefetched weight
         // chunk stay in flight across the phase boundaries.  The one global write -> read inside a workgroup, a' of
@@ -1114,7 +1123,7 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
             gemm_direct16<false>(acc, d1, bq1, xs, ldx_s, IN, lane, d2, bq2);
             if (FWD_BWD) d3.init(P + g.off[2], H, H, col0, lane);
         } else {
-            gemm_tile<TMR, false, DBUF>(acc, st1, xs, ldx_s, IN, Ws, Ws1, tid, col0, st2, H);
+            gemm_tile<TMR, false, DBUF>(acc, st1, xs, ldx_s, K1, Ws, Ws1, tid, col0, st2, H);
         }
         BSTAMP(2);
         if (NSPL == 1 && !CO) stage_first(st2, Ws, H, tid);
@@ -1300,7 +1309,7 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
                     handoff_publish(g.ho.qpub + (int64_t)e * g.n_rows + m0 + tid,
                                     g.ho.base + (g.ho.tick ? (unsigned)*g.ho.tick : 0u), v);
             }
-        } else
+        } else if constexpr (!LEAN)
         // ---- head on the matrix cores: wave w multiplies the k-slice [32w, 32w+32) of h2 with W3^T
         //      (a 16-wide B tile, rows >= OUT zero); the 8 partial tiles are summed through LDS.
         {
@@ -1529,7 +1538,7 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
         else if constexpr (DIRECT_BWD) gemm_direct_nn<TMR>(acc, dnn, h2s, ldh, H, lane);
         else gemm_tile<TMR, true, DBUF>(acc, st3, h2s, ldh, H, Ws, Ws1, tid, col0, none, 0);
         BSTAMP(10);
-        const bool want_dx = MODE == MODE_CRITIC_U && g.DXU != nullptr;
+        const bool want_dx = MODE == MODE_CRITIC_U && !LEAN && g.DXU != nullptr;
         int m1r = 0;
         T::foreach4(acc, lane, [&](int row, int cw, f4 val) {
             const int col = col0 + cw;
@@ -1704,7 +1713,8 @@ void fused_chain_kernel(FusedArgs ga, FusedArgs ga_rest, FusedArgs gt, FusedArgs
 // Producers take the first workgroup ids: they are dispatched before any consumer and never wait, so the polling cannot
 // deadlock whatever part of the grid is resident.  The rank-A update adds a' W1^T after the state columns' sum (the
 // one-pass kernel sums all columns of a K chunk in MFMA order): same value up to fp32 association.
-template <int TC, bool ADBUF, bool AW3LATE = false>
+// CLEAN: the critic tiles run the lean instantiation of the body (fused_mlp_body, LEAN; chosen per launch by ssac_chain_update).
+template <int TC, bool ADBUF, bool AW3LATE = false, bool CLEAN = false>
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_pc_kernel(FusedArgs ga, FusedArgs gt, FusedArgs gc, int tiles_a, int tiles_t, int target_grid_x,
                            int critic_grid_x, DeferredLogsArgs dl, int dl_on, XchgArgs xa, int xchg_on) {
@@ -1768,7 +1778,7 @@ void fused_chain_pc_kernel(FusedArgs ga, FusedArgs gt, FusedArgs gc, int tiles_a
     } else {
         const int c_lo = CRIT_FIRST ? tiles_a : t_hi;
         const int L = ssac_xcd_contiguous_range(bid, c_lo, c_lo + n_crit, gc.xcd);
-        fused_mlp_body<MODE_CRITIC_U, TC, true>(gc, smem, L % critic_grid_x, L / critic_grid_x, critic_grid_x, 32);
+        fused_mlp_body<MODE_CRITIC_U, TC, true, false, false, false, CLEAN>(gc, smem, L % critic_grid_x, L / critic_grid_x, critic_grid_x, 32);
     }
 #ifdef SSAC_LAB
     if (gc.tl && bid < 512) {
@@ -1879,6 +1889,8 @@ long long *g_fused_dbg = nullptr;
 
 int g_tile_rows = 0;  // 0 = automatic, else 16 or 32 (ssac_fused_tile_rows)
 constexpr int CHAIN_FORM_DEFAULT = 0;
+int g_chain_lean = 1;        // ssac_chain_lean: 0 = the chained launch's critic tiles always run the general instantiation
+int g_chain_lean_taken = -1;  // ssac_chain_lean_taken: form of the last ssac_chain_update launch (1 lean, 0 general, -1 none yet)
 int g_chain_form = CHAIN_FORM_DEFAULT;  // ssac_chain_form: 0 = one workgroup per CU (fused_chain_pc_kernel), 1 = the co-resident form where it applies
 
 // co: the co-resident carve (one activation tile instead of two); cons_wa: floats of W1's action columns a CO consumer parks
@@ -2001,7 +2013,8 @@ void patch_slots(int n_args) {
 // The instantiations of one kernel template that a launcher chooses from, keyed by (tile rows, form).  The table is the one
 // place that names them: pick() raises the dynamic-LDS limit of ALL of them on the family's first launch and hands out the
 // one asked for (null + ssac_fail otherwise) -- no instantiation can be launched without having had its limit raised.
-enum { FORM_SINGLE = 0, FORM_DBUF = 1, FORM_LATE = 2 };   // the actor half's weight staging (FORM_LATE: W3LATE, fused_mlp_body)
+enum { FORM_SINGLE = 0, FORM_DBUF = 1, FORM_LATE = 2,     // the actor half's weight staging (FORM_LATE: W3LATE, fused_mlp_body)
+       FORM_LEAN = 4 };   // + the lean critic tile (fused_chain_pc_kernel's CLEAN; 32-row tiles beside a double-buffered actor)
 template <typename... A>
 struct KernelFamily {
     using Fn = void (*)(A...);
@@ -2033,7 +2046,8 @@ KernelFamily<FusedArgs, FusedArgs, FusedArgs, FusedArgs, int, int, int, Deferred
 KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int, int, int, DeferredLogsArgs, int, XchgArgs, int> CHAIN_PC{"fused_chain_pc", {
     {16, FORM_DBUF, fused_chain_pc_kernel<16, true>}, {32, FORM_DBUF, fused_chain_pc_kernel<32, true>},
     {16, FORM_SINGLE, fused_chain_pc_kernel<16, false>}, {32, FORM_SINGLE, fused_chain_pc_kernel<32, false>},
-    {16, FORM_LATE, fused_chain_pc_kernel<16, true, true>}, {32, FORM_LATE, fused_chain_pc_kernel<32, true, true>}}};
+    {16, FORM_LATE, fused_chain_pc_kernel<16, true, true>}, {32, FORM_LATE, fused_chain_pc_kernel<32, true, true>},
+    {32, FORM_DBUF | FORM_LEAN, fused_chain_pc_kernel<32, true, false, true>}}};
 KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int> ACTOR_CHAIN{"fused_actor_chain", {
     {16, FORM_DBUF, fused_actor_chain_kernel<16>}, {32, FORM_DBUF, fused_actor_chain_kernel<32>},
     {16, FORM_SINGLE, fused_actor_chain_kernel<16, false>}, {32, FORM_SINGLE, fused_actor_chain_kernel<32, false>}}};
@@ -2262,7 +2276,15 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
         ga.ho = ho;
         gt.ho = ho;
         if (gather) { gt.gth = *gather; gt.gth_role = 5; }
-        const auto pc_kernel = CHAIN_PC.pick(tc, alate ? FORM_LATE : adbuf ? FORM_DBUF : FORM_SINGLE);
+        // The lean critic tile (fused_mlp_body, LEAN) is chosen per launch, from what this function has looked at anyway, as the
+        // weight-gradient launcher chooses its lean kernel: hidden 256, one head output (checked above), an input of one K
+        // chunk, 32-row tiles, a double-buffered actor beside them, and not the co-resident form.  Everything else takes the
+        // general instantiation -- also a critic tile that is asked for dQ/da (gc.DXU; no caller of this launch sets it
+        // today): the lean body does not compile that tail, so such a launch must not reach it.
+        const bool lean = g_chain_lean && !co_form && tc == 32 && adbuf && critics->hidden == 256 && critics->in_dim <= 32 &&
+                          critics->out_dim == 1 && !gc.DXU;
+        g_chain_lean_taken = lean ? 1 : 0;
+        const auto pc_kernel = CHAIN_PC.pick(tc, (alate ? FORM_LATE : adbuf ? FORM_DBUF : FORM_SINGLE) | (lean ? FORM_LEAN : 0));
         if (!pc_kernel) return 1;
         const int tiles_c = tiles_t * target_splits;   // consumers: one per (slot, column split, tile)
         // critic-sharded rank: the exchange of the subset's target Q as a tail workgroup of THIS launch (xchg != NULL)
@@ -2292,6 +2314,7 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
         if (gather && gather->feed) patch_slots(3);   // ga, gt, gc
         return ssac_check_launch("fused_chain_pc");
     }
+    g_chain_lean_taken = 0;
     if (target_splits != 1) return ssac_fail("ssac_chain_update: column-split target critics need the hand-off form");
     if (xchg) return ssac_fail("ssac_chain_update: the in-launch exchange needs the hand-off (producer / consumer) form");
     const dim3 grid(tiles_t + cgx * critics->n_nets + dl_on);
@@ -2464,6 +2487,13 @@ extern "C" int ssac_chain_form(int form) {
     g_chain_form = form < 0 ? CHAIN_FORM_DEFAULT : form;
     return 0;
 }
+
+extern "C" int ssac_chain_lean(int on) {
+    g_chain_lean = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int ssac_chain_lean_taken(void) { return g_chain_lean_taken; }
 
 extern "C" int ssac_fused_tile_rows(int rows) {
     if (rows != 0 && rows != 16 && rows != 17 && rows != 32)
