@@ -928,9 +928,9 @@ def _member_step(m, c):
 
 
 def _actor_chain_form(a_arena, A, B, c_arena):
-    """does this member's online actor update take the chained launch (ssac_actor_chain_fused)?  ONE predicate for the
-    launch selection in _online_actor_update and for the recording's choice of noise source in online_actor_update: a
-    member on the three-launch form reads its noise from a buffer, which a recording must own and refill before every replay.
+    """does this member's online actor update take the chained launch (ssac_actor_chain_fused)?  Asked by
+    _actor_member_plan alone, which turns it into the member's launch form and noise source: a member on the three-launch
+    form reads its noise from a buffer, which a recording must own and refill before every replay.
     (B <= 2048 = SSAC_ACTOR_CHAIN_MAX_ROWS: the chained launch's actor workgroups wait for critic tiles dispatched behind
     them and must leave them CUs to run on.)
     Round 6: an actor whose carve holds only ONE weight-staging buffer (Humanoid's 376 -> 256 -> 34) can take the chained
@@ -945,38 +945,55 @@ def _actor_chain_form(a_arena, A, B, c_arena):
     return (B + 15) // 16 + tiles_c <= 256
 
 
-def _actor_fused_member(kind, random_process, use_baseline, clip, a_arena, c_arena):
-    """does this member's online actor update take the fused launches at all (the sharded and the unsharded branch of
-    _online_actor_update share it; which of the two is decided by parallel.shard_of at the call site)?"""
-    return bool(FUSED_ACTOR and kind == "stochastic" and random_process is None and not use_baseline and not clip
-                and a_arena.fused and c_arena.fused_dbuf and c_arena.out_dim == 1)
+def _actor_member_plan(kind, random_process, use_baseline, clip, a_arena, c_arena, A, B, sharded, rec_buffers):
+    """THE decision of one member's online actor update, made once: (form, noise).  Everything that has to agree with the
+    launch site asks here -- whether the update can be recorded, where a recording's noise comes from, what a member-
+    sharded rank skips for a member another rank owns.
+    form: "chain" (ssac_actor_chain_fused, _actor_chain_form), "fused" (the three launches; on a critic-sharded rank with
+    the routing and exchange steps between the second and the third), "layers" (the per-layer family).
+    noise: "kernel" (the chained launch with the stock generator draws it from the engine's Philox stream: no buffer, no
+    draw from the device generator), "recording" (the recording's fixed buffers, refilled by the caller before every
+    replay: a recording with a member off the chained launch owns one per member), "draw" (a fresh draw on the host)."""
+    if not (FUSED_ACTOR and kind == "stochastic" and random_process is None and not use_baseline and not clip
+            and a_arena.fused and c_arena.fused_dbuf and c_arena.out_dim == 1):
+        return "layers", "draw"
+    if sharded:   # (every rank makes the same draw)
+        return "fused", "draw"
+    chain = _actor_chain_form(a_arena, A, B, c_arena)
+    if rec_buffers:
+        noise = "recording"
+    else:
+        noise = "kernel" if (chain and lu.IN_KERNEL_NOISE and rng.normal_is_stock()) else "draw"
+    return ("chain" if chain else "fused"), noise
 
 
-def _member_noise_in_kernel(chain, rec_eps):
-    """the chained launch with the stock generator draws the member's noise inside the kernel (no buffer, no draw from
-    the device generator) -- unless a recording owns noise buffers for it"""
-    return bool(chain and lu.IN_KERNEL_NOISE and rng.normal_is_stock() and rec_eps is None)
-
-
-def _actor_noise_in_kernel(agent, batch_size, dev):
-    """recorded actor update: the noise is drawn inside the launches only if EVERY member takes the chained launch.
-    (the arenas' shapes cannot change under a recording, so the per-form answer is cached on the agent; what CAN change
-    between calls -- a noise hook, the IN_KERNEL_NOISE / ACTOR_CHAIN switches -- is re-read every time)"""
-    if not (lu.IN_KERNEL_NOISE and rng.normal_is_stock()):
-        return False
-    key = (batch_size, str(dev), ACTOR_CHAIN, tuple(id(a_) for a_ in agent.actors))
-    memo = agent.__dict__.setdefault("_ssac_chain_form_memo", {})
+def _member_plan(agent, i, B, dev, random_process, use_baseline, clip, rec_buffers=False):
+    """_actor_member_plan of the agent's member i at B rows -> (form, noise, the actor's arena, the critics' arena).  (Keyed by everything the plan reads -- the arenas by their
+    dimensions, the switches and the noise hook by their current values -- the answer is cached on the agent: a replayed
+    update asks on every call.)"""
+    actor = agent.actors[i]
+    a_arena, c_arena = engine.bind_arena(actor, "self", [actor], dev), agent.critics[i].arena(dev)
+    args = (lu.actor_kind(actor), random_process, use_baseline, clip, a_arena, c_arena, actor.action_size, B,
+            parallel.shard_of(agent) is not None, bool(rec_buffers))
+    key = (args[0], random_process is None, bool(use_baseline), bool(clip), a_arena.fused, a_arena.hidden, c_arena.fused_dbuf,
+           c_arena.in_dim, c_arena.hidden, c_arena.out_dim, c_arena.n_nets) + args[6:] + (
+           FUSED_ACTOR, ACTOR_CHAIN, lu.IN_KERNEL_NOISE, rng.normal_is_stock())
+    memo = agent.__dict__.setdefault("_ssac_actor_plan_memo", {})
     if key not in memo:
         if len(memo) > 16:
             memo.clear()
-        memo[key] = all(_actor_chain_form(engine.bind_arena(a_, "self", [a_], dev), a_.action_size, batch_size, c_.arena(dev))
-                        for a_, c_ in zip(agent.actors, agent.critics))
-    return memo[key]
+        memo[key] = _actor_member_plan(*args)
+    return memo[key] + (a_arena, c_arena)
 
 
 class _RecordedActor:
+    """one recorded online actor update: calls so far, the launch list, its fixed log block (blk) with the logs' word index,
+    the noise buffers it owns (eps; None: in_kernel), and per call the log ring's buffer (ring) and this call's slot of it;
+    published: the recorded log step writes the finished block to that slot itself"""
+    __slots__ = ("calls", "list", "blk", "eps", "index", "in_kernel", "published", "ring", "slot")
+
     def __init__(self):
-        self.calls, self.list, self.blk, self.eps, self.index = 0, None, None, None, None
+        self.calls, self.list, self.blk, self.eps, self.index, self.ring, self.slot = 0, None, None, None, None, None, 0
         self.in_kernel = False
         self.published = False
 
@@ -993,7 +1010,10 @@ def online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_s
                         per=False, discrete=False, use_baseline=False):
     """learning.py:344-421.  On the fused path (continuous stochastic actor, no clipping / exploration process /
     baseline) the update is four launches + a log launch; called repeatedly on the batch buffers of a recorded critic
-    update (premade_replay_dicts at fixed addresses) it is recorded after two calls and re-issued from ONE C call."""
+    update (premade_replay_dicts at fixed addresses) it is recorded after two calls and re-issued from ONE C call.
+    Which launch form a member takes and where its noise comes from is decided in ONE place, _actor_member_plan: the
+    test below for "can be recorded", the recording's choice of noise source and the launch site in
+    _online_actor_update all read its answer."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
     kw = dict(buffer=buffer, agent=agent, pop=pop, actor_optimizer=actor_optimizer, log_alphas=log_alphas,
@@ -1007,13 +1027,12 @@ def online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_s
             beta.refuse("online_actor_update on a critic- or member-sharded agent")
     dev = log_alphas[0].device
     recordable = (USE_GRAPHS and LAUNCH_MODE == "list" and FUSED_ACTOR and engine.CAPTURE is None
-                  and premade_replay_dicts is not None and not discrete and not clip and random_process is None
-                  and not use_baseline and parallel.shard_of(agent) is None
-                  and parallel.member_shard_of(agent) is None and lu.is_identity(agent.encoder)
-                  and all(lu.actor_kind(a_) == "stochastic" and engine.bind_arena(a_, "self", [a_], dev).fused
-                          for a_ in agent.actors)
-                  and all(c_.arena(dev).fused_dbuf and c_.arena(dev).out_dim == 1 for c_ in agent.critics))
-    if not recordable:
+                  and premade_replay_dicts is not None and not discrete and parallel.shard_of(agent) is None
+                  and parallel.member_shard_of(agent) is None and lu.is_identity(agent.encoder))
+    # ... and every member on a fused form
+    plans = recordable and [_member_plan(agent, i, batch_size, dev, random_process, use_baseline, clip)[:2]
+                            for i in range(len(agent.actors))]
+    if not plans or any(form == "layers" for form, _ in plans):
         return _online_actor_update(**kw)
     ptrs = tuple(lu.encode(agent.encoder, rd_["primary_batch"][0]).data_ptr() for rd_ in premade_replay_dicts)
     key = (id(actor_optimizer), ptrs, batch_size, bool(pop), tuple(id(la_) for la_ in log_alphas), engine.USE_FUSED)
@@ -1028,74 +1047,71 @@ def online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_s
         return _online_actor_update(**kw)
     A = agent.actors[0].action_size
     ring = lu.ring_for(dev)
+    # the chained launch (ACTOR_CHAIN) with the stock generator draws its noise in the kernel: no buffers, no launches
+    # (... if every member takes it: a member on the three-launch form reads a buffer this recording must own)
+    in_kernel = all(noise == "kernel" for _, noise in plans)
     if rec.list is None:
         rec.blk = torch.zeros(lu.LOG_WIDTH, device=dev)
-        # the chained launch (ACTOR_CHAIN) with the stock generator draws its noise in the kernel: no buffers, no launches
-        # (... if every member takes it: a member on the three-launch form reads a buffer this recording must own)
-        rec.in_kernel = _actor_noise_in_kernel(agent, batch_size, dev)
+        rec.in_kernel = in_kernel
         rec.eps = None if rec.in_kernel else [torch.empty(batch_size, A, device=dev) for _ in agent.actors]
-    elif rec.in_kernel != _actor_noise_in_kernel(agent, batch_size, dev):
+    elif rec.in_kernel != in_kernel:
         # a noise hook was installed / removed (or the form switched) since the recording: record again
         del cache[key]
         return online_actor_update(**kw)
     if rec.eps is not None:
         for e_ in rec.eps:
             rng.draw_normal_into(e_)  # a_dist.rsample() of every member, in member order (learning.py:392)
-    slot_i = ring.advance()   # this call's slot of the log ring
+    rec.ring, rec.slot = ring.buf, ring.advance()   # this call's slot of the log ring
     if rec.list is None:
-        pub = {"buf": ring.buf, "slot": slot_i, "published": False}
         check(lib.ssac_record_begin())
         try:
-            logs = _online_actor_update(**kw, _rec_blk=rec.blk, _rec_eps=rec.eps, _rec_ring=pub)
+            logs = _online_actor_update(**kw, rec=rec)
         finally:
             rec.list = lib.ssac_record_end()
-        rec.published = pub["published"]   # (the log launch writes the ring slot itself: single-member agents)
         base = rec.blk.data_ptr()
         rec.index = {k_: (v.data_ptr() - base) // 4 for k_, v in logs.items()}
     else:
         ns_upd = lu.noise_stream(agent, dev)
         # (this update's number: tags, noise draws -- and, when the log launch publishes, the ring slot it writes)
         if rec.published:
-            check(lib.ssac_replay_value2(rec.list, engine.stream(), ns_upd[2], slot_i))
+            check(lib.ssac_replay_value2(rec.list, engine.stream(), ns_upd[2], rec.slot))
         else:
             check(lib.ssac_replay_value(rec.list, engine.stream(), ns_upd[2]))
         ns_upd[2] += 1
         rng.choice(agent.actors)  # learning.py:417-419 (keeps the Python RNG stream in step)
     if not rec.published:
-        ring.buf[slot_i].copy_(rec.blk)   # this call's log block -> its own ring slot (device-to-device, no sync)
-    blk = ring.buf[slot_i]
+        ring.buf[rec.slot].copy_(rec.blk)   # this call's log block -> its own ring slot (device-to-device, no sync)
+    blk = ring.buf[rec.slot]
     return {k_: blk[i] for k_, i in rec.index.items()}
+
+
+class _ActorMember:
+    """ONE ensemble member's online actor update: i / ig (local / global member index), actor and a_arena, c_arena (its
+    critics), popart, log_alpha, rd (replay dict), s_rep with its row stride lds, and the plan: form, noise"""
+    __slots__ = ("i", "ig", "actor", "a_arena", "c_arena", "popart", "log_alpha", "rd", "s_rep", "lds", "form", "noise")
 
 
 def _online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_size, clip,
                          random_process, noise_clip, augmenter, aug_mix, premade_replay_dicts=None,
-                         per=False, discrete=False, use_baseline=False, _rec_blk=None, _rec_eps=None, _rec_ring=None):
-    E = agent.ensemble_size
-    dev = log_alphas[0].device
-    ws = lu.agent_ws(agent, dev)
-    adam = engine.adam_group(actor_optimizer, dev)
-    # a RECORDED update clears its (fixed) log block and advances the Adam step by a recorded launch: the chained launch of
-    # the first member does it (ACTOR_CHAIN), or a begin launch in front
-    begin_folded = _rec_blk is not None and ACTOR_CHAIN
-    if _rec_blk is not None:
-        slot = _rec_blk
-        if not begin_folded:
-            check(lib.ssac_begin_update(slot.data_ptr(), lu.LOG_WIDTH, adam.ctl.ptr, 0, engine.stream()))
-    else:
-        slot = lu.log_block(dev, adam)
+                         per=False, discrete=False, use_baseline=False, rec=None):
+    """the ensemble-level flow; rec: the _RecordedActor whose launches are being recorded (None: an eager call)"""
+    c = types.SimpleNamespace(**locals())   # the call: its arguments, and below what every member shares
+    dev = c.dev = log_alphas[0].device
+    ws = c.ws = lu.agent_ws(agent, dev)
+    adam = c.adam = engine.adam_group(actor_optimizer, dev)
+    # (a RECORDED update clears its fixed log block and advances the Adam step by a recorded launch of its first member)
+    slot = c.slot = rec.blk if rec is not None else lu.log_block(dev, adam)
     # this update's number: hand-off tags and in-kernel noise draws of the chained launches (checkpointed with the agent's
     # noise stream, so a resumed run continues the sequence)
-    ns_upd = lu.noise_stream(agent, dev)
-    first_fused = True
-    logs = {}
-    st = engine.stream()
+    ns_upd = c.ns_upd = lu.noise_stream(agent, dev)
+    st = c.st = engine.stream()
     # member-sharded rank (parallel.MemberShard): the loss is averaged over the GLOBAL ensemble (learning.py:409), and the
     # members other ranks own still take their host draws here, in member order
     ms = parallel.member_shard_of(agent)
-    E_glob = len(agent.actors) if ms is None else ms.ensemble_size
-    inv_e = 1.0 / E_glob
-    clip_members, member_ss = [], []
-    members = list(zip(agent.ensemble, agent.popart, log_alphas))
+    E_glob = c.E_glob = len(agent.actors) if ms is None else ms.ensemble_size
+    c.inv_e = 1.0 / E_glob
+    c.clip_members, member_ss = [], []
+    rec_buffers = rec is not None and rec.eps is not None
     for ig in range(E_glob):
         i = ig if ms is None else ms.local(ig)
         if i is None:
@@ -1104,312 +1120,264 @@ def _online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_
                 lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter, aug_mix=aug_mix, per=per)
             # (what the member's owner consumes from the device generator: nothing when its chained launch draws the noise
             # in the kernel -- members share their shapes, so this rank's first member answers for the absent one)
-            a0_, c0_ = agent.actors[0], agent.critics[0]
-            ar0_, cr0_ = engine.bind_arena(a0_, "self", [a0_], dev), c0_.arena(dev)
-            owner_in_kernel = (_actor_fused_member(lu.actor_kind(a0_), random_process, use_baseline, clip, ar0_, cr0_)
-                               and parallel.shard_of(agent) is None
-                               and _member_noise_in_kernel(_actor_chain_form(ar0_, a0_.action_size, batch_size, cr0_), _rec_eps))
-            if not owner_in_kernel:
+            if _member_plan(agent, 0, batch_size, dev, random_process, use_baseline, clip, rec_buffers)[1] != "kernel":
                 lu.skip_actor_draws(agent.actors[0], batch_size, dev, random_process)
             continue
-        (actor, critic), popart, log_alpha = members[i]
+        m = _ActorMember()
+        m.i, m.ig, m.popart, m.log_alpha = i, ig, agent.popart[i], log_alphas[i]
         if premade_replay_dicts is not None:
-            rd = premade_replay_dicts[i]
+            m.rd = premade_replay_dicts[i]
         else:
-            rd = lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter,
-                                            aug_mix=aug_mix, per=per)
-        o = rd["primary_batch"][0]
-        s_rep = lu.encode(agent.encoder, o)  # no gradient to the encoder (learning.py:378-380)
-        B, S = s_rep.shape
-        lds = lu._row_stride(s_rep)
-        a_arena = engine.bind_arena(actor, "self", [actor], dev)
-        c_arena = critic.arena(dev)
-        N = c_arena.n_nets
-        kind = lu.actor_kind(actor)
-        pp, dopop = (popart.ptr if popart else 0), (1 if (popart and pop) else 0)
-        shard = parallel.shard_of(agent)
-        fused_member = _actor_fused_member(kind, random_process, use_baseline, clip, a_arena, c_arena)
-        if fused_member and shard is not None:
-            # ---- critic-sharded rank: the same fused launches, cut at the two exchange steps of SURVEY 8(e) -- sample +
-            #      [s|a] rows; the LOCAL critics' forward + dQ/da; local arg-min, MIN over the ranks, the global arg-min's
-            #      owner keeps its dQ/da row, SUM over the ranks; actor backward on (global min Q, routed dQ/da)
-            A, H = actor.action_size, a_arena.hidden
-            xpi = ws.get(f"au.x{i}", (B, S + A))
-            logp = ws.get(f"au.logp{i}", (B,))
-            ah1, ah2 = ws.get(f"au.a{i}.h1", (1, B, H)), ws.get(f"au.a{i}.h2", (1, B, H))
-            aout = ws.get(f"au.a{i}.y", (1, B, 2 * A))
-            eps = rng.draw_normal((B, A), dev)  # a_dist.rsample() (learning.py:392): every rank makes the same draw
-            check(lib.ssac_actor_sample_concat_fused(C.byref(a_arena.desc()), s_rep.data_ptr(), lds, B, eps.data_ptr(),
-                                                     float(actor.log_std_low), float(actor.log_std_high),
-                                                     xpi.data_ptr(), S + A, logp.data_ptr(), ah1.data_ptr(),
-                                                     ah2.data_ptr(), aout.data_ptr(), 0, st))
-            q = ws.get(f"au.c{i}.y", (N, B, 1))
-            dxu = ws.get(f"au.dxu{i}", (N, B, A))
-            check(lib.ssac_critic_fwd_dx_fused(C.byref(c_arena.desc()), xpi.data_ptr(), S + A, B, S, A, q.data_ptr(),
-                                               dxu.data_ptr(), st))
-            qloc, qglob = ws.get(f"au.qloc{i}", (B,)), ws.get(f"au.qmin{i}", (B,))
-            dsel = ws.get(f"au.da{i}", (1, B, A))
-            check(lib.ssac_actor_route_local(q.data_ptr(), dxu.data_ptr(), N, B, A, qloc.data_ptr(), qglob.data_ptr(),
-                                             dsel.data_ptr(), st))
-            parallel.all_reduce_min(qglob)
-            # (bit-equal minima on two ranks: the lowest rank keeps the row, as torch.min keeps the first index)
-            claim = ws.get(f"au.claim{i}", (B,))
-            check(lib.ssac_actor_route_claim(qloc.data_ptr(), qglob.data_ptr(), B, shard.rank, claim.data_ptr(), st))
-            parallel.all_reduce_min(claim)
-            check(lib.ssac_actor_route_mask(claim.data_ptr(), shard.rank, B, A, dsel.data_ptr(), st))
-            parallel.all_reduce_sum(dsel)
-            tiles = int(lib.ssac_fused_row_tiles(C.byref(a_arena.desc()), B, 1))
-            parts = ws.get(f"au.parts{i}", (tiles,))
-            d_out = ws.get(f"au.dout{i}", (1, B, 2 * A))
-            dz2, dz1 = ws.get(f"au.a{i}.dz2", (1, B, H)), ws.get(f"au.a{i}.dz1", (1, B, H))
-            check(lib.ssac_actor_bwd_fused(C.byref(a_arena.desc()), ah1.data_ptr(), ah2.data_ptr(), B, qglob.data_ptr(), 1,
-                                           dsel.data_ptr(), aout.data_ptr(), eps.data_ptr(), logp.data_ptr(),
-                                           log_alpha.data_ptr(), 1, float(actor.log_std_low),
-                                           float(actor.log_std_high), inv_e, pp, dopop, d_out.data_ptr(),
-                                           dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), st))
-            ttot = engine.wgrad_tiles_total(a_arena)
-            ss = ws.get(f"au.ss{i}", (ttot,))
-            one = E_glob == 1   # (then the logged actor is this one: both logs in one launch)
-            # (a recorded update of a single-member agent: the log step also writes the finished block to its slot of the log
-            #  ring -- the replay names the slot, ssac_replay_value2 -- instead of a copy launch behind every replay)
-            pub = _rec_ring if (one and _rec_ring is not None and _rec_blk is not None) else None
-            folded = False
-            if one and engine.actor_fold_applies(a_arena, None, ss, None, None, None):
-                # ... and the log step itself rides in the weight-gradient launch: its last workgroup to finish sums the
-                # tiles' loss terms and the gradient-norm partials (ssac_actor_logs' arithmetic), no launch of its own
-                done = ws.get(f"au.logdone{i}", (1,), dtype=torch.int32, zero=True)
-                af = _lib.ActorLogFold(done.data_ptr(), parts.data_ptr(), tiles, B, inv_e, lu.LOG_WIDTH,
-                                       slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr(), slot.data_ptr(),
-                                       pub["buf"].data_ptr() if pub else 0, pub["slot"] if pub else 0)
-                folded = bool(engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam,
-                                                  adam_key=("actor", i), sumsq=ss, actor_fold=af))
-            if not folded:
-                engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam,
-                                    adam_key=("actor", i), sumsq=ss)
-                check(lib.ssac_actor_logs(parts.data_ptr(), tiles, B, inv_e, ss.data_ptr() if one else 0, ss.numel(),
-                                          slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr() if one else 0,
-                                          slot.data_ptr(), lu.LOG_WIDTH, pub["buf"].data_ptr() if pub else 0,
-                                          pub["slot"] if pub else 0, st))
-            if pub is not None:
-                pub["published"] = True
-            member_ss.append(None if one else ss)
-            continue
-        if fused_member and shard is None:
-            # ---- four launches instead of ~15 (include/ssac_hip.h, "the online actor update"): sample + [s|a] rows,
-            #      critics' forward + unscaled dQ/da, arg-min routing + tanh-normal backward + actor backward-data,
-            #      weight gradients + Adam; then one launch for the two log values
-            A, H = actor.action_size, a_arena.hidden
-            xpi = ws.get(f"au.x{i}", (B, S + A))
-            logp = ws.get(f"au.logp{i}", (B,))
-            ah1, ah2 = ws.get(f"au.a{i}.h1", (1, B, H)), ws.get(f"au.a{i}.h2", (1, B, H))
-            aout = ws.get(f"au.a{i}.y", (1, B, 2 * A))
-            # the noise: with the stock generator the chained launch takes it from the engine's Philox stream INSIDE the
-            # kernel (draw number = this update's number: no generator launch, no buffer); otherwise a draw -- into the
-            # recording's fixed buffer, or a fresh one -- as a_dist.rsample() makes it (learning.py:392)
-            chain = _actor_chain_form(a_arena, A, B, c_arena)
-            in_kernel = _member_noise_in_kernel(chain, _rec_eps)
-            eps = None   # (kept alive to the end of the member's launches: the kernels read it asynchronously)
-            if in_kernel:
-                eps_ptr = 0
-            elif _rec_eps is not None:
-                eps = _rec_eps[i]   # recorded update: the draw was written into a fixed buffer by the caller
-                eps_ptr = eps.data_ptr()
-            else:
-                # (never inside a recording: a replay would re-read a buffer long returned to the allocator)
-                assert _rec_blk is None, "recorded actor update: the noise must come from the kernel or from the recording's buffers"
-                eps = rng.draw_normal((B, A), dev)
-                eps_ptr = eps.data_ptr()
-            q = ws.get(f"au.c{i}.y", (N, B, 1))
-            dxu = ws.get(f"au.dxu{i}", (N, B, A))
-            tiles = int(lib.ssac_fused_row_tiles(C.byref(a_arena.desc()), B, 1))
-            parts = ws.get(f"au.parts{i}", (tiles,))
-            d_out = ws.get(f"au.dout{i}", (1, B, 2 * A))
-            dz2, dz1 = ws.get(f"au.a{i}.dz2", (1, B, H)), ws.get(f"au.a{i}.dz1", (1, B, H))
-            if chain:
-                ho = ws.get(f"au.handoff{i}", (int(lib.ssac_actor_chain_handoff_words(B, N, A)),), dtype=torch.int64,
-                            zero=True)
-                rs = None
-                if in_kernel:
-                    # (its own stream: the critic updates number their draws from the same seed)
-                    # (the GLOBAL member index: a member-sharded rank draws its members' noise as the unsharded run does)
-                    rs = _lib.Rng((ns_upd[0] ^ 0x5DEECE66D1CEB00C) & (2 ** 64 - 1), 0, (ig << 40) + ns_upd[2])
-                fold = begin_folded and first_fused
-                check(lib.ssac_actor_chain_fused(
-                    C.byref(a_arena.desc()), s_rep.data_ptr(), lds, B, eps_ptr, C.byref(rs) if rs is not None else None,
-                    float(actor.log_std_low), float(actor.log_std_high), xpi.data_ptr(), S + A, logp.data_ptr(),
-                    ah1.data_ptr(), ah2.data_ptr(), aout.data_ptr(), C.byref(c_arena.desc()), q.data_ptr(),
-                    dxu.data_ptr(), log_alpha.data_ptr(), 1, inv_e, pp, dopop, d_out.data_ptr(), dz2.data_ptr(),
-                    dz1.data_ptr(), parts.data_ptr(), ho.data_ptr(), ns_upd[2],
-                    slot.data_ptr() if fold else 0, lu.LOG_WIDTH if fold else 0, adam.ctl.ptr if fold else 0, st))
-            else:
-                if begin_folded and first_fused:   # (a member the chained launch does not take: the begin launch after all)
-                    check(lib.ssac_begin_update(slot.data_ptr(), lu.LOG_WIDTH, adam.ctl.ptr, 0, st))
-                check(lib.ssac_actor_sample_concat_fused(C.byref(a_arena.desc()), s_rep.data_ptr(), lds, B, eps_ptr,
-                                                         float(actor.log_std_low), float(actor.log_std_high),
-                                                         xpi.data_ptr(), S + A, logp.data_ptr(), ah1.data_ptr(),
-                                                         ah2.data_ptr(), aout.data_ptr(), 0, st))
-                check(lib.ssac_critic_fwd_dx_fused(C.byref(c_arena.desc()), xpi.data_ptr(), S + A, B, S, A, q.data_ptr(),
-                                                   dxu.data_ptr(), st))
-                check(lib.ssac_actor_bwd_fused(C.byref(a_arena.desc()), ah1.data_ptr(), ah2.data_ptr(), B, q.data_ptr(), N,
-                                               dxu.data_ptr(), aout.data_ptr(), eps_ptr, logp.data_ptr(),
-                                               log_alpha.data_ptr(), 1, float(actor.log_std_low),
-                                               float(actor.log_std_high), inv_e, pp, dopop, d_out.data_ptr(),
-                                               dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), st))
-            first_fused = False
-            ttot = engine.wgrad_tiles_total(a_arena)
-            ss = ws.get(f"au.ss{i}", (ttot,))
-            one = E_glob == 1   # (then the logged actor is this one: both logs in one launch)
-            # (a recorded update of a single-member agent: the log step also writes the finished block to its slot of the log
-            #  ring -- the replay names the slot, ssac_replay_value2 -- instead of a copy launch behind every replay)
-            pub = _rec_ring if (one and _rec_ring is not None and _rec_blk is not None) else None
-            folded = False
-            if one and engine.actor_fold_applies(a_arena, None, ss, None, None, None):
-                # ... and the log step itself rides in the weight-gradient launch: its last workgroup to finish sums the
-                # tiles' loss terms and the gradient-norm partials (ssac_actor_logs' arithmetic), no launch of its own
-                done = ws.get(f"au.logdone{i}", (1,), dtype=torch.int32, zero=True)
-                af = _lib.ActorLogFold(done.data_ptr(), parts.data_ptr(), tiles, B, inv_e, lu.LOG_WIDTH,
-                                       slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr(), slot.data_ptr(),
-                                       pub["buf"].data_ptr() if pub else 0, pub["slot"] if pub else 0)
-                folded = bool(engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam,
-                                                  adam_key=("actor", i), sumsq=ss, actor_fold=af))
-            if not folded:
-                engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam,
-                                    adam_key=("actor", i), sumsq=ss)
-                check(lib.ssac_actor_logs(parts.data_ptr(), tiles, B, inv_e, ss.data_ptr() if one else 0, ss.numel(),
-                                          slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr() if one else 0,
-                                          slot.data_ptr(), lu.LOG_WIDTH, pub["buf"].data_ptr() if pub else 0,
-                                          pub["slot"] if pub else 0, st))
-            if pub is not None:
-                pub["published"] = True
-            member_ss.append(None if one else ss)
-            continue
-        ah1, ah2, aout = engine.mlp_forward(a_arena, s_rep, lds, 0, B, ws, f"au.a{i}")
-        if kind == "discrete":
-            A = a_arena.out_dim
-            _, _, q = engine.mlp_forward(c_arena, s_rep, lds, 0, B, ws, f"au.c{i}", save=False)
-            if shard is not None:  # elementwise min over the local critics, then over the ranks
-                qm = ws.get(f"au.qmin{i}", (1, B, A))
-                lu._min_over_nets(q, N, B * A, qm)
-                parallel.all_reduce_min(qm)
-                q, N = qm, 1
-            d_out = ws.get(f"au.dout{i}", (1, B, A))
-            check(lib.ssac_discrete_actor_loss_bwd(aout.data_ptr(), q.data_ptr(), N, B, A,
-                                                   log_alpha.data_ptr(), pp, dopop, inv_e,
-                                                   d_out.data_ptr(), slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
-        else:
-            A = actor.action_size
-            xpi = lu._concat_buffer(ws, f"au.x{i}", s_rep, A)
-            logp = ws.get(f"au.logp{i}", (B,))
-            eps = rng.draw_normal((B, A), dev) if kind != "beta" else None  # a_dist.rsample() (learning.py:392)
-            if kind == "beta":
-                # a_dist.rsample() of the Beta head; x is kept for the reparameterised backward
-                xb = beta.sample(agent, aout, B, A, "actor", ws.get(f"au.xb{i}", (B, A)), xpi, S + A, S, logp)
-                use_entropy = 1
-                if random_process is not None:
-                    noise = rng.draw_normal((B, A), dev)
-                    check(lib.ssac_exploration_noise(xpi.data_ptr(), S + A, S, noise.data_ptr(),
-                                                     float(random_process.current_scale),
-                                                     float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
-                    use_entropy = 0
-            elif kind == "stochastic":
-                check(lib.ssac_tanh_normal_fwd(aout.data_ptr(), 2 * A, eps.data_ptr(), B, A,
-                                               float(actor.log_std_low), float(actor.log_std_high),
-                                               xpi.data_ptr(), S + A, S, logp.data_ptr(), st))
-                use_entropy = 1
-                if random_process is not None:
-                    # exploration noise on the sampled action, no entropy term (learning.py:393-395); the gradient
-                    # passes through the clamp unchanged (learning_utils.py:56-59)
-                    noise = rng.draw_normal((B, A), dev)
-                    check(lib.ssac_exploration_noise(xpi.data_ptr(), S + A, S, noise.data_ptr(),
-                                                     float(random_process.current_scale),
-                                                     float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
-                    use_entropy = 0
-            elif random_process is not None:
-                noise = rng.draw_normal((B, A), dev)
-                check(lib.ssac_det_action_fwd(aout.data_ptr(), A, eps.data_ptr(), 1e-4, noise.data_ptr(),
-                                              float(random_process.current_scale),
-                                              float(noise_clip) if noise_clip is not None else 0.0, B, A,
-                                              xpi.data_ptr(), S + A, S, st))
-                use_entropy = 0
-            else:
-                # deterministic actor without a process: a = loc + 1e-4 eps, entropy term = its Normal(loc, 1e-4)
-                # log-density (no gradient: a - loc does not depend on the actor; learning.py:396-399)
-                check(lib.ssac_det_action_fwd(aout.data_ptr(), A, eps.data_ptr(), 1e-4, 0, 0.0, 0.0, B, A,
-                                              xpi.data_ptr(), S + A, S, st))
-                check(lib.ssac_det_logprob(eps.data_ptr(), B, A, logp.data_ptr(), st))
-                use_entropy = 1
-            ch1, ch2, q = engine.mlp_forward(c_arena, xpi, S + A, 0, B, ws, f"au.c{i}")
-            dq = ws.get(f"au.dq{i}", (N, B, 1))
-            qmin_ptr = 0
-            if shard is not None:  # min over ALL critics: local min, then MIN all-reduce over ranks
-                qmin = ws.get(f"au.qmin{i}", (B,))
-                lu._min_over_nets(q, N, B, qmin)
-                parallel.all_reduce_min(qmin)
-                qmin_ptr = qmin.data_ptr()
-            if use_baseline:
-                # learning.py:401: vals = A(s, a_theta) = Q'(s, a_theta) - V(s) from the advantage estimator (four fresh
-                # policy samples, drawn after the rsample; adv_estimator.py:31-36 applies the PopArt layer whenever
-                # the member has one).  V has no gradient: the routing of dL/dq is the plain path's.
-                assert shard is None, "use_baseline is not supported on critic-sharded ranks"
-                res = agent.adv_estimator.evaluate(o, xpi[:, S:], i, want=("adv",))
-                check(lib.ssac_actor_loss_bwd_adv(q.data_ptr(), N, B, logp.data_ptr(), log_alpha.data_ptr(),
-                                                  use_entropy, pp, 1 if popart else 0, inv_e,
-                                                  res["adv"].data_ptr(), dq.data_ptr(),
-                                                  slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
-            else:
-                check(lib.ssac_actor_loss_bwd(q.data_ptr(), N, B, logp.data_ptr(), log_alpha.data_ptr(),
-                                              use_entropy, pp, dopop, inv_e, qmin_ptr, dq.data_ptr(),
-                                              slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
-            # dQ/da through the arg-min critic of every row; critic weights are NOT updated here
-            dX = engine.mlp_backward(c_arena, dq, xpi, S + A, 0, ch1, ch2, B, ws, f"au.c{i}",
-                                     need_dx=True, update=False)
-            n_dx, ld_dx, s_dx, col_dx = N, S + A, B * (S + A), S
-            if shard is not None:  # SUM all-reduce of the (B x A) action gradient
-                da = ws.get(f"au.da{i}", (1, B, A))
-                torch.sum(dX[:, :, S:], dim=0, out=da[0])
-                parallel.all_reduce_sum(da)
-                dX, n_dx, ld_dx, s_dx, col_dx = da, 1, A, B * A, 0
-            d_out = ws.get(f"au.dout{i}", (1, B, a_arena.out_dim))
-            if kind == "beta":
-                check(lib.ssac_beta_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), 2 * A,
-                                        xb.data_ptr(), B, A, log_alpha.data_ptr(), use_entropy, inv_e, 0,
-                                        d_out.data_ptr(), 2 * A, st))
-            elif kind == "stochastic":
-                check(lib.ssac_tanh_normal_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(),
-                                               2 * A, eps.data_ptr(), B, A, float(actor.log_std_low),
-                                               float(actor.log_std_high), log_alpha.data_ptr(), use_entropy, inv_e,
-                                               d_out.data_ptr(), 2 * A, st))
-            else:
-                check(lib.ssac_det_action_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), A,
-                                              B, A, d_out.data_ptr(), A, st))
-        ttot = engine.wgrad_tiles_total(a_arena)
-        ss = ws.get(f"au.ss{i}", (ttot,))
-        if clip:
-            grads = ws.get(f"au.g{i}", (a_arena.params.numel(),), zero=True)
-            engine.mlp_backward(a_arena, d_out, s_rep, lds, 0, ah1, ah2, B, ws, f"au.a{i}", grads=grads,
-                                sumsq=ss)
-            clip_members.append((a_arena, ("actor", i), grads, ss))
-        else:
-            engine.mlp_backward(a_arena, d_out, s_rep, lds, 0, ah1, ah2, B, ws, f"au.a{i}", adam=adam,
-                                adam_key=("actor", i), sumsq=ss)
-        member_ss.append(ss)
+            m.rd = lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter,
+                                              aug_mix=aug_mix, per=per)
+        s_rep = m.s_rep = lu.encode(agent.encoder, m.rd["primary_batch"][0])  # no gradient to the encoder (learning.py:378-380)
+        m.lds = lu._row_stride(s_rep)
+        m.actor = agent.actors[i]
+        m.form, m.noise, m.a_arena, m.c_arena = _member_plan(agent, i, s_rep.shape[0], dev, random_process, use_baseline, clip,
+                                                             rec_buffers)
+        member_ss.append(_actor_member_layers(m, c) if m.form == "layers" else _actor_member_fused(m, c))
     ns_upd[2] += 1
+    _step_and_log_norm(agent, adam, clip, c.clip_members, member_ss, slot[lu.L_ACTOR_GN:], ms)
+    return {"gradients/random_actor_online_grad": slot[lu.L_ACTOR_GN], "losses/actor_pg_loss": slot[lu.L_ACTOR_LOSS]}
+
+
+def _actor_member_fused(m, c):
+    """the "chain" and "fused" forms of member m -- four launches instead of ~15 (include/ssac_hip.h, "the online actor
+    update"): sample + [s|a] rows, critics' forward + unscaled dQ/da, arg-min routing + tanh-normal backward + actor
+    backward-data (the three as ONE chained launch on the "chain" form), weight gradients + Adam; then the two log values.
+    -> the member's sum-of-squares slots for the norm launch, None when its own log step wrote the norm already"""
+    ws, st, i, rec, slot, adam, inv_e = c.ws, c.st, m.i, c.rec, c.slot, c.adam, c.inv_e
+    actor, a_arena, c_arena, s_rep, lds, log_alpha = m.actor, m.a_arena, m.c_arena, m.s_rep, m.lds, m.log_alpha
+    (B, S), A, H, N = s_rep.shape, actor.action_size, a_arena.hidden, c_arena.n_nets
+    lo, hi = float(actor.log_std_low), float(actor.log_std_high)
+    pp, dopop = (m.popart.ptr if m.popart else 0), (1 if (m.popart and c.pop) else 0)
+    # ---- work space
+    xpi = ws.get(f"au.x{i}", (B, S + A))
+    logp = ws.get(f"au.logp{i}", (B,))
+    ah1, ah2 = ws.get(f"au.a{i}.h1", (1, B, H)), ws.get(f"au.a{i}.h2", (1, B, H))
+    aout = ws.get(f"au.a{i}.y", (1, B, 2 * A))
+    q = ws.get(f"au.c{i}.y", (N, B, 1))
+    dxu = ws.get(f"au.dxu{i}", (N, B, A))
+    tiles = int(lib.ssac_fused_row_tiles(C.byref(a_arena.desc()), B, 1))
+    parts = ws.get(f"au.parts{i}", (tiles,))
+    d_out = ws.get(f"au.dout{i}", (1, B, 2 * A))
+    dz2, dz1 = ws.get(f"au.a{i}.dz2", (1, B, H)), ws.get(f"au.a{i}.dz1", (1, B, H))
+    # ---- the noise, as a_dist.rsample() makes it (learning.py:392) unless the chained launch draws it in the kernel
+    eps = None   # (kept alive to the end of the member's launches: the kernels read it asynchronously)
+    if m.noise == "recording":
+        eps = rec.eps[i]   # the draw was written into a fixed buffer by the caller
+    elif m.noise == "draw":
+        # (never inside a recording: a replay would re-read a buffer long returned to the allocator)
+        assert rec is None, "recorded actor update: the noise must come from the kernel or from the recording's buffers"
+        eps = rng.draw_normal((B, A), c.dev)
+    eps_ptr = eps.data_ptr() if eps is not None else 0
+    # ---- the launches.  The first member of a RECORDED update also clears the log block and advances the Adam step: inside
+    #      its chained launch, or by a begin launch in front of a member the chained launch does not take
+    begin = rec is not None and m.ig == 0
+    if m.form == "chain":
+        ho = ws.get(f"au.handoff{i}", (int(lib.ssac_actor_chain_handoff_words(B, N, A)),), dtype=torch.int64, zero=True)
+        rs = None
+        if m.noise == "kernel":
+            # (its own stream: the critic updates number their draws from the same seed)
+            # (the GLOBAL member index: a member-sharded rank draws its members' noise as the unsharded run does)
+            rs = _lib.Rng((c.ns_upd[0] ^ 0x5DEECE66D1CEB00C) & (2 ** 64 - 1), 0, (m.ig << 40) + c.ns_upd[2])
+        check(lib.ssac_actor_chain_fused(
+            C.byref(a_arena.desc()), s_rep.data_ptr(), lds, B, eps_ptr, C.byref(rs) if rs is not None else None, lo, hi,
+            xpi.data_ptr(), S + A, logp.data_ptr(), ah1.data_ptr(), ah2.data_ptr(), aout.data_ptr(),
+            C.byref(c_arena.desc()), q.data_ptr(), dxu.data_ptr(), log_alpha.data_ptr(), 1, inv_e, pp, dopop,
+            d_out.data_ptr(), dz2.data_ptr(), dz1.data_ptr(), parts.data_ptr(), ho.data_ptr(), c.ns_upd[2],
+            slot.data_ptr() if begin else 0, lu.LOG_WIDTH if begin else 0, adam.ctl.ptr if begin else 0, st))
+    else:
+        if begin:
+            check(lib.ssac_begin_update(slot.data_ptr(), lu.LOG_WIDTH, adam.ctl.ptr, 0, st))
+        check(lib.ssac_actor_sample_concat_fused(C.byref(a_arena.desc()), s_rep.data_ptr(), lds, B, eps_ptr, lo, hi,
+                                                 xpi.data_ptr(), S + A, logp.data_ptr(), ah1.data_ptr(), ah2.data_ptr(),
+                                                 aout.data_ptr(), 0, st))
+        check(lib.ssac_critic_fwd_dx_fused(C.byref(c_arena.desc()), xpi.data_ptr(), S + A, B, S, A, q.data_ptr(),
+                                           dxu.data_ptr(), st))
+        # (a critic-sharded rank: the actor backward reads the GLOBAL min Q and the dQ/da row routed from its owner)
+        qsel, nsel, dsel = (q, N, dxu) if parallel.shard_of(c.agent) is None else _route_over_ranks(m, c, q, dxu)
+        check(lib.ssac_actor_bwd_fused(C.byref(a_arena.desc()), ah1.data_ptr(), ah2.data_ptr(), B, qsel.data_ptr(), nsel,
+                                       dsel.data_ptr(), aout.data_ptr(), eps_ptr, logp.data_ptr(), log_alpha.data_ptr(), 1,
+                                       lo, hi, inv_e, pp, dopop, d_out.data_ptr(), dz2.data_ptr(), dz1.data_ptr(),
+                                       parts.data_ptr(), st))
+    # ---- weight gradients + Adam, the log step, and (recorded single-member update) the ring slot
+    ss = ws.get(f"au.ss{i}", (engine.wgrad_tiles_total(a_arena),))
+    one = c.E_glob == 1   # (then the logged actor is this one: both logs in one launch)
+    # (a recorded update of a single-member agent: the log step also writes the finished block to its slot of the log
+    #  ring -- the replay names the slot, ssac_replay_value2 -- instead of a copy launch behind every replay)
+    pub = rec if one else None
+    ring_ptr, ring_slot = (pub.ring.data_ptr(), pub.slot) if pub is not None else (0, 0)
+    folded = False
+    if one and engine.actor_fold_applies(a_arena, None, ss, None, None, None):
+        # ... and the log step itself rides in the weight-gradient launch: its last workgroup to finish sums the
+        # tiles' loss terms and the gradient-norm partials (ssac_actor_logs' arithmetic), no launch of its own
+        done = ws.get(f"au.logdone{i}", (1,), dtype=torch.int32, zero=True)
+        af = _lib.ActorLogFold(done.data_ptr(), parts.data_ptr(), tiles, B, inv_e, lu.LOG_WIDTH,
+                               slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr(), slot.data_ptr(),
+                               ring_ptr, ring_slot)
+        folded = bool(engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam,
+                                          adam_key=("actor", i), sumsq=ss, actor_fold=af))
+    if not folded:
+        engine.weight_grads(a_arena, s_rep, lds, 0, ah1, ah2, d_out, dz2, dz1, B, adam=adam, adam_key=("actor", i), sumsq=ss)
+        check(lib.ssac_actor_logs(parts.data_ptr(), tiles, B, inv_e, ss.data_ptr() if one else 0, ss.numel(),
+                                  slot[lu.L_ACTOR_LOSS:].data_ptr(), slot[lu.L_ACTOR_GN:].data_ptr() if one else 0,
+                                  slot.data_ptr(), lu.LOG_WIDTH, ring_ptr, ring_slot, st))
+    if pub is not None:
+        pub.published = True
+    return None if one else ss
+
+
+def _route_over_ranks(m, c, q, dxu):
+    """critic-sharded rank, between the critics' forward and the actor backward -- the two exchange steps of SURVEY 8(e):
+    local arg-min, MIN over the ranks, the global arg-min's owner keeps its dQ/da row, SUM over the ranks.
+    -> (global min Q, 1, routed dQ/da): what ssac_actor_bwd_fused takes in place of (q, N, dxu)"""
+    ws, st, i, rank = c.ws, c.st, m.i, parallel.shard_of(c.agent).rank
+    N, B, A = dxu.shape
+    qloc, qglob = ws.get(f"au.qloc{i}", (B,)), ws.get(f"au.qmin{i}", (B,))
+    dsel = ws.get(f"au.da{i}", (1, B, A))
+    check(lib.ssac_actor_route_local(q.data_ptr(), dxu.data_ptr(), N, B, A, qloc.data_ptr(), qglob.data_ptr(),
+                                     dsel.data_ptr(), st))
+    parallel.all_reduce_min(qglob)
+    # (bit-equal minima on two ranks: the lowest rank keeps the row, as torch.min keeps the first index)
+    claim = ws.get(f"au.claim{i}", (B,))
+    check(lib.ssac_actor_route_claim(qloc.data_ptr(), qglob.data_ptr(), B, rank, claim.data_ptr(), st))
+    parallel.all_reduce_min(claim)
+    check(lib.ssac_actor_route_mask(claim.data_ptr(), rank, B, A, dsel.data_ptr(), st))
+    parallel.all_reduce_sum(dsel)
+    return qglob, 1, dsel
+
+
+def _exploration_noise(c, xpi, S, B, A):
+    """exploration noise on the sampled action, no entropy term (learning.py:393-395); the gradient passes through the
+    clamp unchanged (learning_utils.py:56-59).  -> the draw (the caller keeps it alive: the kernel reads it asynchronously)"""
+    noise = rng.draw_normal((B, A), c.dev)
+    check(lib.ssac_exploration_noise(xpi.data_ptr(), S + A, S, noise.data_ptr(), float(c.random_process.current_scale),
+                                     float(c.noise_clip) if c.noise_clip is not None else 0.0, B, A, c.st))
+    return noise
+
+
+def _actor_member_layers(m, c):
+    """the "layers" form of member m: every actor kind, exploration process, baseline and clip, on the per-layer family.
+    Host draws in the reference's order: rsample noise (Beta: beta.sample in its place), process noise, then the
+    advantage estimator's.  -> the member's sum-of-squares slots"""
+    ws, st, i, slot, inv_e, random_process = c.ws, c.st, m.i, c.slot, c.inv_e, c.random_process
+    actor, a_arena, c_arena, s_rep, lds, log_alpha = m.actor, m.a_arena, m.c_arena, m.s_rep, m.lds, m.log_alpha
+    (B, S), N, kind, shard = s_rep.shape, c_arena.n_nets, lu.actor_kind(actor), parallel.shard_of(c.agent)
+    pp, dopop = (m.popart.ptr if m.popart else 0), (1 if (m.popart and c.pop) else 0)
+    ah1, ah2, aout = engine.mlp_forward(a_arena, s_rep, lds, 0, B, ws, f"au.a{i}")
+    if kind == "discrete":
+        A = a_arena.out_dim
+        _, _, q = engine.mlp_forward(c_arena, s_rep, lds, 0, B, ws, f"au.c{i}", save=False)
+        if shard is not None:  # elementwise min over the local critics, then over the ranks
+            qm = ws.get(f"au.qmin{i}", (1, B, A))
+            lu._min_over_nets(q, N, B * A, qm)
+            parallel.all_reduce_min(qm)
+            q, N = qm, 1
+        d_out = ws.get(f"au.dout{i}", (1, B, A))
+        check(lib.ssac_discrete_actor_loss_bwd(aout.data_ptr(), q.data_ptr(), N, B, A, log_alpha.data_ptr(), pp, dopop,
+                                               inv_e, d_out.data_ptr(), slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
+    else:
+        A = actor.action_size
+        xpi = lu._concat_buffer(ws, f"au.x{i}", s_rep, A)
+        logp = ws.get(f"au.logp{i}", (B,))
+        eps = rng.draw_normal((B, A), c.dev) if kind != "beta" else None  # a_dist.rsample() (learning.py:392)
+        noise = None   # (kept alive to the end of the member's launches)
+        use_entropy = 1 if random_process is None else 0
+        if kind == "beta":
+            # a_dist.rsample() of the Beta head; x is kept for the reparameterised backward
+            xb = beta.sample(c.agent, aout, B, A, "actor", ws.get(f"au.xb{i}", (B, A)), xpi, S + A, S, logp)
+        elif kind == "stochastic":
+            check(lib.ssac_tanh_normal_fwd(aout.data_ptr(), 2 * A, eps.data_ptr(), B, A, float(actor.log_std_low),
+                                           float(actor.log_std_high), xpi.data_ptr(), S + A, S, logp.data_ptr(), st))
+        if kind in ("beta", "stochastic"):
+            if random_process is not None:
+                noise = _exploration_noise(c, xpi, S, B, A)
+        elif random_process is not None:
+            noise = rng.draw_normal((B, A), c.dev)
+            check(lib.ssac_det_action_fwd(aout.data_ptr(), A, eps.data_ptr(), 1e-4, noise.data_ptr(),
+                                          float(random_process.current_scale),
+                                          float(c.noise_clip) if c.noise_clip is not None else 0.0, B, A,
+                                          xpi.data_ptr(), S + A, S, st))
+        else:
+            # deterministic actor without a process: a = loc + 1e-4 eps, entropy term = its Normal(loc, 1e-4)
+            # log-density (no gradient: a - loc does not depend on the actor; learning.py:396-399)
+            check(lib.ssac_det_action_fwd(aout.data_ptr(), A, eps.data_ptr(), 1e-4, 0, 0.0, 0.0, B, A,
+                                          xpi.data_ptr(), S + A, S, st))
+            check(lib.ssac_det_logprob(eps.data_ptr(), B, A, logp.data_ptr(), st))
+        ch1, ch2, q = engine.mlp_forward(c_arena, xpi, S + A, 0, B, ws, f"au.c{i}")
+        dq = ws.get(f"au.dq{i}", (N, B, 1))
+        qmin_ptr = 0
+        if shard is not None:  # min over ALL critics: local min, then MIN all-reduce over ranks
+            qmin = ws.get(f"au.qmin{i}", (B,))
+            lu._min_over_nets(q, N, B, qmin)
+            parallel.all_reduce_min(qmin)
+            qmin_ptr = qmin.data_ptr()
+        if c.use_baseline:
+            # learning.py:401: vals = A(s, a_theta) = Q'(s, a_theta) - V(s) from the advantage estimator (four fresh
+            # policy samples, drawn after the rsample; adv_estimator.py:31-36 applies the PopArt layer whenever
+            # the member has one).  V has no gradient: the routing of dL/dq is the plain path's.
+            assert shard is None, "use_baseline is not supported on critic-sharded ranks"
+            res = c.agent.adv_estimator.evaluate(m.rd["primary_batch"][0], xpi[:, S:], i, want=("adv",))
+            check(lib.ssac_actor_loss_bwd_adv(q.data_ptr(), N, B, logp.data_ptr(), log_alpha.data_ptr(), use_entropy, pp,
+                                              1 if m.popart else 0, inv_e, res["adv"].data_ptr(), dq.data_ptr(),
+                                              slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
+        else:
+            check(lib.ssac_actor_loss_bwd(q.data_ptr(), N, B, logp.data_ptr(), log_alpha.data_ptr(), use_entropy, pp,
+                                          dopop, inv_e, qmin_ptr, dq.data_ptr(), slot[lu.L_ACTOR_LOSS:].data_ptr(), st))
+        # dQ/da through the arg-min critic of every row; critic weights are NOT updated here
+        dX = engine.mlp_backward(c_arena, dq, xpi, S + A, 0, ch1, ch2, B, ws, f"au.c{i}", need_dx=True, update=False)
+        n_dx, ld_dx, s_dx, col_dx = N, S + A, B * (S + A), S
+        if shard is not None:  # SUM all-reduce of the (B x A) action gradient
+            da = ws.get(f"au.da{i}", (1, B, A))
+            torch.sum(dX[:, :, S:], dim=0, out=da[0])
+            parallel.all_reduce_sum(da)
+            dX, n_dx, ld_dx, s_dx, col_dx = da, 1, A, B * A, 0
+        d_out = ws.get(f"au.dout{i}", (1, B, a_arena.out_dim))
+        if kind == "beta":
+            check(lib.ssac_beta_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), 2 * A, xb.data_ptr(), B, A,
+                                    log_alpha.data_ptr(), use_entropy, inv_e, 0, d_out.data_ptr(), 2 * A, st))
+        elif kind == "stochastic":
+            check(lib.ssac_tanh_normal_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), 2 * A,
+                                           eps.data_ptr(), B, A, float(actor.log_std_low), float(actor.log_std_high),
+                                           log_alpha.data_ptr(), use_entropy, inv_e, d_out.data_ptr(), 2 * A, st))
+        else:
+            check(lib.ssac_det_action_bwd(dX.data_ptr(), n_dx, ld_dx, s_dx, col_dx, aout.data_ptr(), A, B, A,
+                                          d_out.data_ptr(), A, st))
+    return _actor_backward(a_arena, d_out, s_rep, lds, ah1, ah2, B, ws, "au", i, c.adam, c.clip, c.clip_members)[1]
+
+
+def _actor_backward(a_arena, d_out, x, ldx, h1, h2, n_rows, ws, pre, i, adam, clip, clip_members, need_dx=False):
+    """backward of actor member i from dL/d(output): into a gradient buffer for the clip (the member joins clip_members),
+    or with Adam in the epilogue of the weight-gradient launch.  -> (dX when need_dx, the member's sum-of-squares slots)"""
+    ss = ws.get(f"{pre}.ss{i}", (engine.wgrad_tiles_total(a_arena),))
+    if clip:
+        grads = ws.get(f"{pre}.g{i}", (a_arena.params.numel(),), zero=True)
+        dX = engine.mlp_backward(a_arena, d_out, x, ldx, 0, h1, h2, n_rows, ws, f"{pre}.a{i}", grads=grads, sumsq=ss,
+                                 need_dx=need_dx)
+        clip_members.append((a_arena, ("actor", i), grads, ss))
+    else:
+        dX = engine.mlp_backward(a_arena, d_out, x, ldx, 0, h1, h2, n_rows, ws, f"{pre}.a{i}", adam=adam,
+                                 adam_key=("actor", i), sumsq=ss, need_dx=need_dx)
+    return dX, ss
+
+
+def _step_and_log_norm(agent, adam, clip, clip_members, member_ss, norm_out, ms=None):
+    """what closes an actor update: clip and step, refresh the bf16 shadows, pick the logged member (the reference's
+    random.choice, learning.py:210-212 / 417-419) and write its gradient norm to norm_out"""
     if clip:
         _clip_and_step(adam, clip_members, clip, None, member_shard=ms)
     for actor in agent.actors:  # bf16 mode: the actor step ran on the fp32 masters; refresh the shadows
         for ar in actor.__dict__.get("_ssac_arenas", {}).values():
             ar.sync_shadow()
     if ms is not None:   # the pick is over the GLOBAL ensemble; a rank that does not hold it logs its first member's norm
-        k = ms.local(rng.choice(range(E_glob))) or 0
+        k = ms.local(rng.choice(range(ms.ensemble_size))) or 0
     else:
-        pick = rng.choice(agent.actors)  # learning.py:417-419
+        pick = rng.choice(agent.actors)
         k = next(j for j, a_ in enumerate(agent.actors) if a_ is pick)
     if member_ss[k] is not None:  # (None: the fused path's log launch wrote the norm already)
-        check(lib.ssac_group_norms(member_ss[k].data_ptr(), 1, member_ss[k].numel(),
-                                   adam.ctl.ptr if clip else 0, slot[lu.L_ACTOR_GN:].data_ptr(), st))
-    logs["gradients/random_actor_online_grad"] = slot[lu.L_ACTOR_GN]
-    logs["losses/actor_pg_loss"] = slot[lu.L_ACTOR_LOSS]
-    return logs
+        check(lib.ssac_group_norms(member_ss[k].data_ptr(), 1, member_ss[k].numel(), adam.ctl.ptr if clip else 0,
+                                   norm_out.data_ptr(), engine.stream()))
 
 
 def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batch_size, actor_clip,
@@ -1542,16 +1510,8 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
                     float(actor.log_std_low), float(actor.log_std_high), float(actor_lambda) * inv_e,
                     d_out[0, B:].data_ptr(), 2 * A, slot[lu.L_ACT_INV:].data_ptr(), slot[lu.L_BC_TOTAL:].data_ptr(), st))
         logs[f"losses/filterd_bc_loss_{i}"] = slot[lu.L_BC0 + i]
-        ttot = engine.wgrad_tiles_total(a_arena)
-        ss = ws.get(f"bc.ss{i}", (ttot,))
-        if actor_clip:
-            grads = ws.get(f"bc.g{i}", (a_arena.params.numel(),), zero=True)
-            dX = engine.mlp_backward(a_arena, d_out, s_rep, lds, 0, ah1, ah2, rows, ws, f"bc.a{i}", grads=grads,
-                                     sumsq=ss, need_dx=enc_grad)
-            clip_members.append((a_arena, ("actor", i), grads, ss))
-        else:
-            dX = engine.mlp_backward(a_arena, d_out, s_rep, lds, 0, ah1, ah2, rows, ws, f"bc.a{i}", adam=adam,
-                                     adam_key=("actor", i), sumsq=ss, need_dx=enc_grad)
+        dX, ss = _actor_backward(a_arena, d_out, s_rep, lds, ah1, ah2, rows, ws, "bc", i, adam, actor_clip, clip_members,
+                                 need_dx=enc_grad)
         if enc_grad and actor_lambda:
             # stacked encoder pass: the BC rows carry a gradient only when the encoder is trained through the BC loss
             # (filtered_bc_loss computes s_rep without gradient otherwise), the augmented rows always do; the encoder
@@ -1567,16 +1527,8 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
             _encoder_step(agent.encoder, encoder_optimizer, encoder_clip, dX, S, ws, slot, dev, accumulate=i > 0,
                           step=i == E - 1)
         member_ss.append(ss)
-    if actor_clip:
-        _clip_and_step(adam, clip_members, actor_clip, None)
-    for actor in agent.actors:
-        for ar in actor.__dict__.get("_ssac_arenas", {}).values():
-            ar.sync_shadow()
     logs["losses/filtered_bc_overall_loss"] = slot[lu.L_BC_TOTAL]
-    pick = rng.choice(agent.actors)  # learning.py:210-212
-    k = next(j for j, a_ in enumerate(agent.actors) if a_ is pick)
-    check(lib.ssac_group_norms(member_ss[k].data_ptr(), 1, member_ss[k].numel(),
-                               adam.ctl.ptr if actor_clip else 0, slot[lu.L_BC_GN:].data_ptr(), st))
+    _step_and_log_norm(agent, adam, actor_clip, clip_members, member_ss, slot[lu.L_BC_GN:])
     logs["gradients/actor_offline_grad_norm"] = slot[lu.L_BC_GN]
     logs["gradients/encoder_offline_actorloss_grad_norm"] = slot[lu.L_ENC_GN]  # identity encoders: no gradient
     if per:

@@ -1010,3 +1010,64 @@ def test_actor_update_chained_launch_matches_three_launches():
     want = torch.tanh(mu + sd * eps)
     got = ws.get("au.x0", (B, S + A))[:, S:]
     assert torch.allclose(got, want, atol=2e-6), float((got - want).abs().max())
+
+
+# launches in the recorded list of ONE online actor update (stock generator; obs 17, act 6, hidden 64, 4 critics, B 128),
+# counted at commit 65950e7, the parent of the host refactor that introduced learning._actor_member_plan.  A host refactor
+# issues the same launches: the margin is zero.
+_ACTOR_LIST_SIZE = {"chained": 2, "three_launches": 5, "two_members": 7}
+
+
+@pytest.mark.parametrize("setting", sorted(_ACTOR_LIST_SIZE))
+def test_recorded_actor_update_is_what_the_member_plan_says(setting):
+    """the recording of an online actor update follows learning._actor_member_plan: its noise is in-kernel exactly when the
+    plan of EVERY member says so, it owns noise buffers exactly when it is not, and its launch list is as long as the one
+    the same setting recorded before the plan existed"""
+    import copy, math, random
+    from itertools import chain
+    import torch
+    import super_sac_amd as ssa
+    L = ssa.learning
+    dev = torch.device("cuda")
+    B, S, A, N, H, E = 128, 17, 6, 4, 64, 2 if setting == "two_members" else 1
+    old_chain, L.ACTOR_CHAIN = L.ACTOR_CHAIN, setting != "three_launches"
+    try:
+        torch.manual_seed(3); np.random.seed(3); random.seed(3)
+        agent = ssa.Agent(act_space_size=A, encoder=ssa.nets.IdentityEncoder(S),
+                          actor_network_cls=ssa.nets.ContinuousStochasticActor, critic_network_cls=ssa.nets.ContinuousCritic,
+                          ensemble_size=E, num_critics=N, hidden_size=H, auto_rescale_targets=False, log_std_low=-5.0,
+                          log_std_high=2.0)
+        agent.to(dev)
+        target = copy.deepcopy(agent)
+        buf = ssa.replay.ReplayBuffer(4096, device=dev)
+        buf.load_experience(*synth.synth_transitions(2000, S, A, seed=5))
+        copt = torch.optim.Adam(chain(*(c.parameters() for c in agent.critics)), lr=3e-4)
+        aopt = torch.optim.Adam(chain(*(a.parameters() for a in agent.actors)), lr=3e-4)
+        eopt = torch.optim.Adam(agent.encoder.parameters(), lr=1e-4)
+        las = []
+        for _ in range(E):
+            la = torch.Tensor([math.log(0.1)]).to(dev); la.requires_grad = True
+            las.append(la)
+        aug = ssa.augmentations.AugmentationSequence([ssa.augmentations.IdentityAug(B)])
+        for _ in range(4):   # (the critic update records after three calls: fixed batch buffers for the actor update)
+            _, dicts = L.critic_update(
+                buffer=buf, agent=agent, target_agent=target, critic_optimizer=copt, encoder_optimizer=eopt, log_alphas=las,
+                batch_size=B, gamma=0.99, critic_clip=None, encoder_clip=None, target_critic_ensemble_n=2,
+                weighted_bellman_temp=None, weight_type=None, pop=False, augmenter=aug, encoder_lambda=0, aug_mix=0.0,
+                discrete=False, random_process=None, noise_clip=None, per=False, update_priorities=False, dr3_coeff=0.0)
+        for _ in range(4):   # two eager calls, the recording, one replay
+            L.online_actor_update(buffer=buf, agent=agent, pop=False, actor_optimizer=aopt, log_alphas=las, batch_size=B,
+                                  clip=None, random_process=None, noise_clip=None, augmenter=aug, aug_mix=0.0,
+                                  premade_replay_dicts=dicts)
+        rec = next(iter(agent.__dict__["_ssac_actor_rec"].values()))
+        plans = [L._actor_member_plan("stochastic", None, False, None, ssa.engine.bind_arena(a_, "self", [a_], dev),
+                                      c_.arena(dev), A, B, False, False) for a_, c_ in zip(agent.actors, agent.critics)]
+        assert all(form == ("fused" if setting == "three_launches" else "chain") for form, _ in plans), plans
+        assert rec.list is not None and rec.in_kernel == all(noise == "kernel" for _, noise in plans)
+        assert rec.in_kernel == (setting != "three_launches")
+        assert (rec.eps is None) == rec.in_kernel
+        n = int(ssa._lib.lib.ssac_launch_list_size(rec.list))
+        print(setting, "launch list size", n)
+        assert n == _ACTOR_LIST_SIZE[setting], (setting, n)
+    finally:
+        L.ACTOR_CHAIN = old_chain
