@@ -7,6 +7,7 @@ reference become ensemble-batched HIP launches -- forward of all N critics in th
 hand-derived backward, and weight-gradient GEMMs whose epilogue is the Adam step -- and the
 logs stay on the device until somebody reads them.
 """
+import collections
 import ctypes as C
 import operator
 import os
@@ -150,23 +151,122 @@ USE_GRAPHS = True   # replay the critic update's launch sequence as one HIP grap
 GRAPH_WARMUP = 3    # eager calls before capture (workspace allocation, arena binding, kernel attributes)
 
 
-class _Graphed:
-    def __init__(self):
-        self.calls = 0
-        self.graph = None
-        self.fast = None
-        self.path = "slow"
-        self.deferred = None   # ssac_deferred_logs of the recording (deferred log finalisation), else None
-        self.pending = None    # log-ring slot of the newest update whose block has not been written yet
+class _SlotLayout(collections.namedtuple(
+        "_SlotLayout", "B n_sub n_pad ids_off logslot_off draw_off nbytes slot_words logslot_word")):
+    """byte layout of one slot of a recorded critic update's input ring, from (B, n_sub):
+        [B int64 replay indices | n_pad int32 subset ids | int32 log-ring slot, int32 pad | int64 noise draw number]
+    n_pad = n_sub rounded up to 8 bytes; ids_off, logslot_off, draw_off = where the last three start; nbytes = the slot
+    rounded up to whole 16-byte words (ssac_feed contract); slot_words, logslot_word = nbytes and logslot_off in the
+    4-byte words ssac_feed counts in.  The ONE place that knows it: the staging and device views, ssac_feed, the capture's
+    draw-number address and ssac_step_create all read these fields (tests/test_critic_recording_cpu.py holds them to
+    ssac_step_create's geometry check)."""
+    __slots__ = ()
 
-    def views(self, ring, slot_i):
-        """log values of ring slot slot_i (built once per slot)"""
+    def __new__(cls, B, n_sub):
+        n_pad = (n_sub + 1) // 2 * 2
+        logslot_off = 8 * B + 4 * n_pad
+        nbytes = (logslot_off + 16 + 15) // 16 * 16
+        return super().__new__(cls, B, n_sub, n_pad, 8 * B, logslot_off, logslot_off + 8, nbytes, nbytes // 4, logslot_off // 4)
+
+    def host_views(self, stage):
+        """of a (slots, nbytes) uint8 numpy array: indices (slots, B) int64, [ids..., log slot at [n_pad], pad]
+        (slots, n_pad + 2) int32, draw number (slots, 1) int64"""
+        return (stage[:, :self.ids_off].view(np.int64), stage[:, self.ids_off:self.draw_off].view(np.int32),
+                stage[:, self.draw_off:self.draw_off + 8].view(np.int64))
+
+
+class _FeedRing:
+    """the input ring of a recorded update (ssac_feed_ring_alloc): device-resident on large-BAR systems"""
+
+    def __init__(self, nbytes):
+        p, d = C.c_void_p(), C.c_int()
+        check(lib.ssac_feed_ring_alloc(nbytes, C.byref(p), C.byref(d)))
+        self.ptr, self.device_resident = p.value, bool(d.value)
+
+    def __del__(self):
+        try:
+            lib.ssac_feed_ring_free(self.ptr, int(self.device_resident))
+        except Exception:
+            pass
+
+
+class _RecordedCritic:
+    """one recorded critic update of an agent (agent.__dict__["_ssac_graphs"][key]), every field it ever holds.
+    The call: refs pins the objects whose ids are in the key (buffer, target agent, critic optimizer, log_alpha).
+    The inputs, made once by prepare() (feed is None before) -- what follows from the call and the agent: dev, log_ring
+    (the device's LogRing), shard and n_critics (the GLOBAL ensemble); and the fixed addresses: layout (_SlotLayout); inbuf, the device block
+    the first launch pulls a slot into, with its views idx_dev / ids_dev; stage, the host copy of the ring the slots are
+    composed in, with np_idx / np_i32 / np_draw; ring (_FeedRing); feed (the ssac_feed struct on the device); eps_dev
+    (injected noise, stochastic actors; else None); logblk (the log block the launches write); late_word (late-bound
+    Polyak decision word, or None).
+    What a recording produced, dropped by drop_recording() (graph is None: nothing recorded): graph (_LaunchList or
+    CUDAGraph), dicts (the replay dicts handed back), members (the MemberUpdate records a replay reads), log_index
+    ({log key: word of logblk}), log_views ({ring slot: {log key: 0-dim view}}), in_kernel_noise (the noise source it was
+    recorded with), deferred (its ssac_deferred_logs, None: logs finalised at once), late_arenas ((target, online) arenas
+    of the late-bound Polyak, or None), td_stats.
+    Progress: fast (the _FastStep over the recording's launch lists; None: not built, retired because a parameter moved, or
+    dropped with its recording), calls (critic_update calls with this key, warm-up included), k (updates issued on the ring, by either
+    replayer), path ("fast": the C step issued the last one, "slow": Python did), pending (log-ring slot of the newest
+    update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path)."""
+    __slots__ = ("refs", "dev", "log_ring", "shard", "n_critics",
+                 "layout", "inbuf", "idx_dev", "ids_dev", "stage", "np_idx", "np_i32", "np_draw", "ring", "feed", "eps_dev",
+                 "logblk", "late_word",
+                 "graph", "dicts", "members", "log_index", "log_views", "in_kernel_noise", "deferred", "late_arenas",
+                 "td_stats", "fast",
+                 "calls", "k", "path", "pending", "events")
+
+    def __init__(self, refs):
+        for f in self.__slots__:
+            setattr(self, f, None)
+        self.refs = refs
+        self.members, self.log_views, self.in_kernel_noise = [], {}, False
+        self.calls, self.k, self.path = 0, 0, "slow"
+
+    def prepare(self, agent, B, n_sub):
+        """One fixed device block holds the per-update inputs (_SlotLayout).  The host writes them into slot k % FEED_SLOTS
+        of the input ring; the first recorded launch pulls the slot in (ssac_feed in include/ssac_hip.h), so an update is
+        ONE graph launch and no copy node."""
+        dev = self.dev = self.refs[3].device
+        self.log_ring = lu.ring_for(dev)
+        self.shard = parallel.shard_of(agent)
+        self.n_critics = agent.num_critics if self.shard is None else self.shard.num_critics
+        lay = self.layout = _SlotLayout(B, n_sub)
+        self.inbuf = torch.zeros(lay.nbytes, dtype=torch.uint8, device=dev)
+        self.idx_dev = self.inbuf[:lay.ids_off].view(torch.int64)
+        self.ids_dev = self.inbuf[lay.ids_off:lay.logslot_off].view(torch.int32)[:n_sub]
+        # the slots are composed in ordinary host memory (numpy views: a fraction of the cost of torch indexing) and
+        # copied into the input ring with ONE ssac_feed_write each; the ring itself is uncached device memory the
+        # host stores into over the PCIe BAR when the system allows it, pinned host memory otherwise
+        self.stage = np.zeros((FEED_SLOTS, lay.nbytes), np.uint8)
+        self.np_idx, self.np_i32, self.np_draw = lay.host_views(self.stage)
+        self.ring = _FeedRing(FEED_SLOTS * lay.nbytes)
+        self.events = [None] * (FEED_SLOTS // EVENT_EVERY)
+        actor = agent.actors[0]
+        self.eps_dev = (torch.empty(B, actor.action_size, device=dev) if lu.actor_kind(actor) == "stochastic" else None)
+        self.logblk = torch.zeros(lu.LOG_WIDTH, device=dev)
+        # late-bound Polyak (include/ssac_hip.h): the decision word the update's first launch writes
+        self.late_word = torch.zeros(4, dtype=torch.int32, device=dev) if lu.LATE_POLYAK else None
+        self.feed = engine.DeviceStruct(_lib.Feed(self.ring.ptr, self.inbuf.data_ptr(), self.log_ring.buf.data_ptr(), 0,
+                                                  FEED_SLOTS, lay.slot_words, lay.logslot_word, lu.LOG_WIDTH,
+                                                  self.late_word.data_ptr() if self.late_word is not None else 0), dev)
+
+    def drop_recording(self):
+        """record again (a noise hook was installed or removed since): forget what the recording produced, the C step
+        that borrows its launch lists included; the inputs and the progress stay.  The retired step stays in
+        agent.__dict__["_ssac_fast"] until the next one takes its key: _FastStep.still_valid's `gs.fast is not self` is what
+        keeps it from running over the freed lists."""
+        lu.flush_pending_logs(self)  # (while the old recording's device structs are alive)
+        self.graph = self.dicts = self.log_index = self.deferred = self.late_arenas = self.td_stats = self.fast = None
+        self.members, self.log_views, self.in_kernel_noise = [], {}, False
+
+    def views(self, slot_i):
+        """log values of log-ring slot slot_i (built once per slot)"""
         v = self.log_views.get(slot_i)
         if v is None:
             if self.deferred is not None:
-                v = lu.lazy_views(self, ring, slot_i, self.log_index)
+                v = lu.lazy_views(self, self.log_ring, slot_i, self.log_index)
             else:
-                blk = ring.buf[slot_i]
+                blk = self.log_ring.buf[slot_i]
                 v = {k_: blk[i] for k_, i in self.log_index.items()}
             self.log_views[slot_i] = v
         return v
@@ -210,17 +310,11 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     cache = agent.__dict__.setdefault("_ssac_graphs", {})  # lives and dies with the agent
     gs = cache.get(key)
     if gs is None:
-        gs = cache[key] = _Graphed()
-        gs.refs = (buffer, target_agent, critic_optimizer, log_alphas[0])  # pin the ids used in the key
+        gs = cache[key] = _RecordedCritic((buffer, target_agent, critic_optimizer, log_alphas[0]))  # the key's ids, pinned
     gs.calls += 1
     if gs.calls <= GRAPH_WARMUP or len(buffer) < batch_size:
         return _critic_update_eager(**kw)
-    out = _critic_update_graphed(gs, kw)
-    if (gs.graph is not None and LAUNCH_MODE == "list" and getattr(gs, "fast", None) is None
-            and all(not callable(p_) for p_ in gs.graph.parts)):
-        gs.fast = _FastStep(gs, kw)
-        agent.__dict__.setdefault("_ssac_fast", {})[_fast_key(kw)] = gs.fast
-    return out
+    return _critic_update_graphed(gs, kw)
 
 
 _fast_values = operator.itemgetter("batch_size", "gamma", "critic_clip", "encoder_clip", "target_critic_ensemble_n",
@@ -239,11 +333,37 @@ def _slot_codes(row, ids, shard):
         row[j] = v if shard is None else shard.slot_code(v)
 
 
-def _recorded_result(gs, idx_cpu, ids, logs):
+def _host_inputs(gs, buffer, agent, in_kernel_noise):
+    """what the host contributes to one recorded update, whoever re-issues it: the reference's host-RNG draws in its order
+    (indices -> (augmentation: none here) -> injected noise -> REDQ subset of the GLOBAL ensemble), the update's log-ring
+    slot, a sharded rank's exchange check, the draw number of the agent's noise stream (one draw per update, as eager)"""
+    lay = gs.layout
+    buffer.total_sample_calls += 1
+    idx_cpu = rng.draw_indices(len(buffer), lay.B)
+    if gs.eps_dev is not None and not in_kernel_noise:
+        rng.draw_normal_into(gs.eps_dev)  # injected noise (parity tests) goes straight into the update's input buffer
+    ids = rng.draw_subset(gs.n_critics, lay.n_sub)
+    slot_i = gs.log_ring.advance()
+    if gs.shard is not None and gs.k % EVENT_EVERY == 0:
+        parallel.check_exchange()
+    draw = 0
+    if in_kernel_noise:
+        ns = lu.noise_stream(agent, gs.dev)
+        draw = ns[1]
+        ns[1] += 1
+    return idx_cpu, ids, slot_i, draw
+
+
+def _close_update(gs, agent, idx_cpu, ids, slot_i):
+    """the update has been issued: count it, keep the Python RNG stream in step, hand out this slot's log views"""
+    gs.k += 1
+    if gs.deferred is not None:
+        gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
+    rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
     rd = gs.dicts[0]
     rd["priority_idxs"] = idx_cpu.numpy()
     rd["_subset"] = ids
-    return logs, gs.dicts
+    return dict(gs.views(slot_i)), gs.dicts
 
 
 def _flush_other_recordings(agent, keep=None):
@@ -257,36 +377,31 @@ def _flush_other_recordings(agent, keep=None):
 
 class _FastStep:
     """the recorded critic update behind ONE C call per update (ssac_step_run, include/ssac_hip.h): what stays in
-    Python is the reference's host-RNG draws, in its order (indices -> injected noise -> REDQ subset -> logged-net
-    choice), and handing out the log views of this update's ring slot"""
+    Python is _host_inputs and _close_update; the C step composes the slot, keeps the slot-reuse events and re-issues
+    the launch lists.  Built over a recording whose lists have no host callable between them."""
 
     def __init__(self, gs, kw):
         self.gs, self.kw = gs, kw
         self.buffer, self.agent = kw["buffer"], kw["agent"]
-        self.B, self.n_sub = kw["batch_size"], kw["target_critic_ensemble_n"]
-        self.dev = kw["log_alphas"][0].device
-        self.ring = lu.ring_for(self.dev)
-        B, n_pad = self.B, gs.n_pad
-        draw_off = 8 * B + 4 * n_pad + 8
-        h = lib.ssac_step_create(gs.ring.ptr, FEED_SLOTS, gs.slot_bytes, B, self.n_sub, 8 * B, 8 * B + 4 * n_pad,
-                                 draw_off, EVENT_EVERY)
+        lay = gs.layout
+        self.B = lay.B
+        h = lib.ssac_step_create(gs.ring.ptr, FEED_SLOTS, lay.nbytes, lay.B, lay.n_sub, lay.ids_off, lay.logslot_off,
+                                 lay.draw_off, EVENT_EVERY)
         if not h:
             raise RuntimeError("libssac_hip: " + lib.ssac_last_error().decode())
         self.handle = h
         for part in gs.graph.parts:
             check(lib.ssac_step_add_list(h, part))
-        self.ids_c = (C.c_int32 * max(self.n_sub, 1))()
-        self.shard = parallel.shard_of(self.agent)
-        self.n_critics = self.agent.num_critics if self.shard is None else self.shard.num_critics  # GLOBAL ensemble
+        self.ids_c = (C.c_int32 * max(lay.n_sub, 1))()
         self.in_kernel_noise = gs.in_kernel_noise
-        self.late_arenas = getattr(gs, "late_arenas", None)   # (target arena, online arena) of the late-bound Polyak
+        self.late_arenas = gs.late_arenas   # (target arena, online arena) of the late-bound Polyak
         self.calls = 0
         # a few parameter addresses checked on every call (cheap), all of them every 256 calls
         actor = self.agent.actors[0]
         tgt = kw["target_agent"]
-        self.arenas = [(self.agent.critics[0].arena(self.dev), list(self.agent.critics[0].nets)),
-                       (tgt.critics[0].arena(self.dev), list(tgt.critics[0].nets)),
-                       (engine.bind_arena(actor, "self", [actor], self.dev), [actor])]
+        self.arenas = [(self.agent.critics[0].arena(gs.dev), list(self.agent.critics[0].nets)),
+                       (tgt.critics[0].arena(gs.dev), list(tgt.critics[0].nets)),
+                       (engine.bind_arena(actor, "self", [actor], gs.dev), [actor])]
         self.probes = []
         for arena, mods in self.arenas:
             lins = engine.MlpArena.linear_triples(mods[0]) + engine.MlpArena.linear_triples(mods[-1])
@@ -295,8 +410,8 @@ class _FastStep:
         # the log views of every ring slot, built now (~7 ms, once): built on a slot's first visit they cost the first
         # 512 replayed updates ~11 us of host time each -- 30 us per step instead of 17, enough to starve the device in
         # short bursts right after recording (tools/burst_parts.py)
-        for slot_i in range(self.ring.buf.shape[0]):
-            gs.views(self.ring, slot_i)
+        for slot_i in range(gs.log_ring.buf.shape[0]):
+            gs.views(slot_i)
 
     def still_valid(self):
         gs = self.gs
@@ -317,7 +432,7 @@ class _FastStep:
         return True
 
     def run(self):
-        gs, buffer, agent = self.gs, self.buffer, self.agent
+        gs, agent = self.gs, self.agent
         if gs.path != "fast":
             # the Python path issued updates of this recording since: line the step up with the ring's device counter
             # (its slot-reuse events know nothing about those updates, so let them finish first)
@@ -326,29 +441,12 @@ class _FastStep:
             gs.path = "fast"
         if len(agent.__dict__["_ssac_graphs"]) > 1:
             _flush_other_recordings(agent, keep=gs)
-        buffer.total_sample_calls += 1
-        idx_cpu = rng.draw_indices(len(buffer), self.B)
-        if gs.eps_dev is not None and not self.in_kernel_noise:
-            rng.draw_normal_into(gs.eps_dev)  # injected noise (parity tests)
-        ids = rng.draw_subset(self.n_critics, self.n_sub)
-        ida, sh = self.ids_c, self.shard
-        _slot_codes(ida, ids, sh)
-        slot_i = self.ring.advance()
-        if sh is not None and gs.k % EVENT_EVERY == 0:
-            parallel.check_exchange()
-        draw = 0
-        if self.in_kernel_noise:
-            ns = lu.noise_stream(agent, self.dev)
-            draw = ns[1]
-            ns[1] += 1
-        check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), ida, slot_i, draw, engine.stream()))
-        gs.k += 1
+        idx_cpu, ids, slot_i, draw = _host_inputs(gs, self.buffer, agent, self.in_kernel_noise)
+        _slot_codes(self.ids_c, ids, gs.shard)
+        check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, draw, engine.stream()))
         if self.late_arenas is not None:
             agent.critics[0].__dict__["_ssac_last_step"] = self   # a soft_update that follows needs no launch
-        if gs.deferred is not None:
-            gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
-        rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
-        return _recorded_result(gs, idx_cpu, ids, dict(gs.views(self.ring, slot_i)))
+        return _close_update(gs, agent, idx_cpu, ids, slot_i)
 
     def __del__(self):
         try:
@@ -357,190 +455,143 @@ class _FastStep:
             pass
 
 
-class _FeedRing:
-    """the input ring of a recorded update (ssac_feed_ring_alloc): device-resident on large-BAR systems"""
-
-    def __init__(self, nbytes):
-        p, d = C.c_void_p(), C.c_int()
-        check(lib.ssac_feed_ring_alloc(nbytes, C.byref(p), C.byref(d)))
-        self.ptr, self.device_resident = p.value, bool(d.value)
-
-    def __del__(self):
-        try:
-            lib.ssac_feed_ring_free(self.ptr, int(self.device_resident))
-        except Exception:
-            pass
-
-
 def _critic_update_graphed(gs, kw):
-    buffer, agent, B = kw["buffer"], kw["agent"], kw["batch_size"]
+    """one update of a recording from Python: the recording call itself, the hipGraph mode, lists with a collective
+    between segments, and whatever the C step (_FastStep) does not serve"""
+    buffer, agent = kw["buffer"], kw["agent"]
     agent.critics[0].__dict__.pop("_ssac_last_step", None)
     if gs.path == "fast":  # (the C step's slot-reuse events are not visible from here)
         torch.cuda.synchronize()
         gs.path = "slow"
-    dev = kw["log_alphas"][0].device
+    if gs.feed is None:
+        gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"])
     actor = agent.actors[0]
-    kind = lu.actor_kind(actor)
-    n_sub = kw["target_critic_ensemble_n"]
-    ring = lu.ring_for(dev)
-    if gs.graph is None and getattr(gs, "feed", None) is None:
-        # one fixed device block holds the per-update inputs:
-        #   [B int64 indices | n int32 subset ids (padded to 8 bytes) | int32 log-ring slot, int32 pad]
-        # The host writes them into slot k % FEED_SLOTS of a pinned ring; the first captured launch pulls the
-        # slot over PCIe (ssac_feed in include/ssac_hip.h), so an update is ONE graph launch and no copy node.
-        n_pad = (n_sub + 1) // 2 * 2
-        # ... | int64 draw number of the agent's noise stream]; slots are whole 16-byte words (ssac_feed contract)
-        nbytes = (8 * B + 4 * n_pad + 16 + 15) // 16 * 16
-        gs.inbuf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        gs.idx_dev = gs.inbuf[:8 * B].view(torch.int64)
-        gs.ids_dev = gs.inbuf[8 * B:8 * B + 4 * n_pad].view(torch.int32)[:n_sub]
-        # the slots are composed in ordinary host memory (numpy views: a fraction of the cost of torch indexing) and
-        # copied into the input ring with ONE ssac_feed_write each; the ring itself is uncached device memory the
-        # host stores into over the PCIe BAR when the system allows it, pinned host memory otherwise
-        gs.stage = np.zeros((FEED_SLOTS, nbytes), np.uint8)
-        gs.ring = _FeedRing(FEED_SLOTS * nbytes)
-        gs.slot_bytes = nbytes
-        hnp = gs.stage
-        gs.np_idx = hnp[:, :8 * B].view(np.int64)                           # (slots, B)
-        gs.np_i32 = hnp[:, 8 * B:8 * B + 4 * n_pad + 8].view(np.int32)      # ids..., then the log slot at [n_pad]
-        gs.np_draw = hnp[:, 8 * B + 4 * n_pad + 8:8 * B + 4 * n_pad + 16].view(np.int64)  # (slots, 1)
-        gs.n_pad = n_pad
-        gs.log_views = {}
-        gs.events = [None] * FEED_SLOTS
-        gs.k = 0
-        gs.eps_dev = torch.empty(B, actor.action_size, device=dev) if kind == "stochastic" else None
-        gs.logblk = torch.zeros(lu.LOG_WIDTH, device=dev)
-        # late-bound Polyak (include/ssac_hip.h): the decision word the update's first launch writes
-        gs.late_word = torch.zeros(4, dtype=torch.int32, device=dev) if lu.LATE_POLYAK else None
-        gs.feed = engine.DeviceStruct(_lib.Feed(gs.ring.ptr, gs.inbuf.data_ptr(), ring.buf.data_ptr(), 0,
-                                                FEED_SLOTS, nbytes // 4, (8 * B + 4 * n_pad) // 4,
-                                                lu.LOG_WIDTH,
-                                                gs.late_word.data_ptr() if gs.late_word is not None else 0), dev)
-    # ---- host draws, in the reference's order: indices -> (augmentation: none here) -> noise -> subset
-    buffer.total_sample_calls += 1
-    idx_cpu = rng.draw_indices(len(buffer), B)
     # (the in-kernel stream is used by the fused actor-sample launch only: wide action heads take the per-layer path)
-    in_kernel_noise = (kind == "stochastic" and lu.IN_KERNEL_NOISE and rng.normal_is_stock()
-                       and engine.bind_arena(actor, "self", [actor], dev).fused)
+    in_kernel_noise = (lu.actor_kind(actor) == "stochastic" and lu.IN_KERNEL_NOISE and rng.normal_is_stock()
+                       and engine.bind_arena(actor, "self", [actor], gs.dev).fused)
     if gs.graph is not None and gs.in_kernel_noise != in_kernel_noise:
-        lu.flush_pending_logs(gs)  # (while the old recording's device structs are alive)
-        gs.graph = None  # a noise hook was installed / removed since the recording: record the update again
-        gs.feed = None
+        gs.drop_recording()
     _flush_other_recordings(agent, keep=gs if gs.graph is not None else None)
-    if kind == "stochastic" and not in_kernel_noise:
-        # injected noise (parity tests) goes straight into the captured update's input buffer
-        rng.draw_normal_into(gs.eps_dev)
-    shard = parallel.shard_of(agent)
-    ids = rng.draw_subset(agent.num_critics if shard is None else shard.num_critics, n_sub)  # GLOBAL ensemble
-    # ---- per-update inputs into this update's pinned slot
-    k = gs.k % FEED_SLOTS
-    # slot reuse: the replay that read this slot FEED_SLOTS updates ago must have finished.  One event per group of
-    # EVENT_EVERY updates (recorded after the group's last update; an event costs a barrier packet on the queue)
-    if gs.k % EVENT_EVERY == 0 and gs.k >= FEED_SLOTS:
-        gs.events[((gs.k - FEED_SLOTS) // EVENT_EVERY) % (FEED_SLOTS // EVENT_EVERY)].synchronize()
-    if shard is not None and gs.k % EVENT_EVERY == 0:
-        parallel.check_exchange()
-    slot_i = ring.advance()
-    gs.np_idx[k] = idx_cpu.numpy()
-    row = gs.np_i32[k]
-    _slot_codes(row, ids, shard)
-    row[gs.n_pad] = slot_i
-    if in_kernel_noise:
-        gs.np_draw[k, 0] = lu.noise_stream(agent, dev)[1]
-    check(lib.ssac_feed_write(gs.ring.ptr + k * gs.slot_bytes, gs.stage.ctypes.data + k * gs.slot_bytes, gs.slot_bytes))
+    idx_cpu, ids, slot_i, draw = _host_inputs(gs, buffer, agent, in_kernel_noise)
+    _write_slot(gs, idx_cpu, ids, slot_i, draw)
     if gs.graph is None:
-        gs.in_kernel_noise = in_kernel_noise
-        ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev,
-                                [gs.eps_dev] if (gs.eps_dev is not None and not in_kernel_noise) else [],
-                                gs.logblk, feed=gs.feed.ptr)
-        if in_kernel_noise:
-            # the draw number travels in the input slot, so recorded and eager updates of an agent may interleave
-            ctx.tick_ptr = gs.inbuf.data_ptr() + 8 * B + 4 * gs.n_pad + 8
-            ctx.noise_offset = 0
-        st_ = buffer._storage
-        keys_ = list(st_.s_stack.keys())
-        # vector observations in one array: the whole-transition gather is the update's first launch and takes
-        # over ssac_begin_update's work (ensemble_size 1: a single gather per update)
-        ctx.defer_begin = (FOLD_BEGIN and agent.ensemble_size == 1 and len(keys_) == 1
-                           and st_.s_stack[keys_[0]].dim() == 2)
-        c_arena_ = agent.critics[0].arena(dev)
-        if (lu.DEFERRED_LOGS and LAUNCH_MODE == "list" and FOLD_LOGS and _loss_folds(B) and LAZY_TD and ctx.defer_begin
-                and not kw["critic_clip"] and kind == "stochastic" and not any(agent.popart) and c_arena_.out_dim == 1):
-            # deferred log finalisation (csrc/ssac_critic_logs.h): the buffers the weight-gradient launch will leave
-            # its partials in are workspace tensors with fixed names, so the struct can be built before the body runs
-            ws_ = lu.agent_ws(agent, dev)
-            N_ = c_arena_.n_nets
-            ttot_ = (engine.bf16_tiles_total(c_arena_) if c_arena_.shadow is not None
-                     else engine.wgrad_tiles_total(c_arena_))
-            n_glob_ = N_ if shard is None else shard.num_critics
-            gs.td_stats = ws_.get("cu.tdstats", (4,), zero=True)
-            ctx.deferred = _lib.DeferredLogs(
-                ws_.get("cu.c0.fparts", (N_ * 2,)).data_ptr(), N_, N_ * ttot_, ws_.get("cu.ss0", (N_ * ttot_,)).data_ptr(),
-                gs.td_stats.data_ptr(), lu.L_TD0, B, float(n_glob_), 0, gs.feed.ptr)
-            t_arena_ = kw["target_agent"].critics[0].arena(dev)
-            if (gs.late_word is not None and (c_arena_.shadow is None) == (t_arena_.shadow is None)
-                    and t_arena_.params.numel() == c_arena_.params.numel()):
-                # late-bound Polyak: the weight-gradient launch carries the target arena and waits for the decision
-                ctx.late = gs.late_word.data_ptr()
-                ctx.late_target = t_arena_
-
-        gs.members = []   # the members' records: what a replay reads lives as long as the recording
-
-        def body():
-            logs_, dicts_ = _critic_update_eager(_records=gs.members, **kw)
-            assert not ctx.pending_begin, "deferred ssac_begin_update was never issued"
-            assert ctx.deferred_used == ctx.deferred_chain, "deferred log finalisation: chain / weight-gradient mismatch"
-            gs.deferred = ctx.deferred if ctx.deferred_used else None
-            gs.late_arenas = ((ctx.late_target, agent.critics[0].arena(dev))
-                              if (ctx.deferred_used and ctx.late_used) else None)
-            if not ctx.published:
-                check(lib.ssac_publish_logs(gs.logblk.data_ptr(), gs.feed.ptr, engine.stream()))
-            return logs_, dicts_
-        engine.CAPTURE = ctx
-        try:
-            if LAUNCH_MODE == "graph":
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    logs, dicts = body()
-                graph.replay()
-            else:
-                # launch list: this call's launches run normally AND are recorded for the later calls
-                graph = _LaunchList()
-
-                def collective(fn):
-                    graph.add_list(lib.ssac_record_end())
-                    fn()
-                    graph.parts.append(fn)
-                    check(lib.ssac_record_begin())
-                ctx.collective = collective
-                check(lib.ssac_record_begin())
-                try:
-                    logs, dicts = body()
-                finally:
-                    handle = lib.ssac_record_end()
-                graph.add_list(handle)
-        finally:
-            engine.CAPTURE = None
-        gs.graph, gs.dicts = graph, dicts
-        base = gs.logblk.data_ptr()
-        gs.log_index = {k_: (v.data_ptr() - base) // 4 for k_, v in logs.items()}
-        gs.log_views = {}   # the 0-dim views handed out as log values, built once per ring slot (gs.views)
+        _record(gs, kw, idx_cpu, ids, in_kernel_noise)   # (the launches run now AND are recorded)
     else:
         gs.graph.replay()  # ONE host call re-issues the whole update
+    _mark_group(gs)
+    out = _close_update(gs, agent, idx_cpu, ids, slot_i)
+    if gs.fast is None and LAUNCH_MODE == "list" and all(not callable(p_) for p_ in gs.graph.parts):
+        gs.fast = agent.__dict__.setdefault("_ssac_fast", {})[_fast_key(kw)] = _FastStep(gs, kw)
+    return out
+
+
+def _write_slot(gs, idx_cpu, ids, slot_i, draw):
+    """the Python replayer's half of ssac_step_run, before the launches: update gs.k's inputs into its slot of the ring"""
+    k = gs.k
+    # slot reuse: the replay that read this slot FEED_SLOTS updates ago must have finished.  One event per group of
+    # EVENT_EVERY updates (recorded after the group's last update; an event costs a barrier packet on the queue).  No
+    # event: the C step issued that group, and the switch away from it synchronised the device.
+    ev = gs.events[((k - FEED_SLOTS) // EVENT_EVERY) % len(gs.events)]
+    if k % EVENT_EVERY == 0 and k >= FEED_SLOTS and ev is not None:
+        ev.synchronize()
+    s, nbytes = k % FEED_SLOTS, gs.layout.nbytes
+    gs.np_idx[s] = idx_cpu.numpy()
+    row = gs.np_i32[s]
+    _slot_codes(row, ids, gs.shard)
+    row[gs.layout.n_pad] = slot_i
+    gs.np_draw[s, 0] = draw
+    check(lib.ssac_feed_write(gs.ring.ptr + s * nbytes, gs.stage.ctypes.data + s * nbytes, nbytes))
+
+
+def _mark_group(gs):
+    """... and behind them: the event of a group of EVENT_EVERY updates follows its last update"""
     if gs.k % EVENT_EVERY == EVENT_EVERY - 1:
-        gi = (gs.k // EVENT_EVERY) % (FEED_SLOTS // EVENT_EVERY)
-        ev = gs.events[gi]
-        if ev is None:
-            ev = gs.events[gi] = torch.cuda.Event()
-        ev.record()
-    gs.k += 1
+        gi = (gs.k // EVENT_EVERY) % len(gs.events)
+        if gs.events[gi] is None:
+            gs.events[gi] = torch.cuda.Event()
+        gs.events[gi].record()
+
+
+def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
+    """run the update once with its launches recorded (a launch list, cut into segments around the collectives of a
+    sharded rank, or a hipGraph) against the record's fixed-address inputs, and fill in what the recording produced"""
+    buffer, agent, B, dev = kw["buffer"], kw["agent"], kw["batch_size"], gs.dev
+    kind = lu.actor_kind(agent.actors[0])
+    gs.in_kernel_noise = in_kernel_noise
+    ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev,
+                            [gs.eps_dev] if (gs.eps_dev is not None and not in_kernel_noise) else [],
+                            gs.logblk, feed=gs.feed.ptr)
     if in_kernel_noise:
-        lu.noise_stream(agent, dev)[1] += 1  # one draw of the agent's noise stream per update, as in eager launches
-    rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
-    if gs.deferred is not None:
-        gs.pending = slot_i
-    return _recorded_result(gs, idx_cpu, ids, dict(gs.views(ring, slot_i)))
+        ctx.tick_ptr = gs.inbuf.data_ptr() + gs.layout.draw_off
+        ctx.noise_offset = 0
+    st_ = buffer._storage
+    keys_ = list(st_.s_stack.keys())
+    # vector observations in one array: the whole-transition gather is the update's first launch and takes
+    # over ssac_begin_update's work (ensemble_size 1: a single gather per update)
+    ctx.defer_begin = (FOLD_BEGIN and agent.ensemble_size == 1 and len(keys_) == 1
+                       and st_.s_stack[keys_[0]].dim() == 2)
+    c_arena_ = agent.critics[0].arena(dev)
+    if (lu.DEFERRED_LOGS and LAUNCH_MODE == "list" and FOLD_LOGS and _loss_folds(B) and LAZY_TD and ctx.defer_begin
+            and not kw["critic_clip"] and kind == "stochastic" and not any(agent.popart) and c_arena_.out_dim == 1):
+        # deferred log finalisation (csrc/ssac_critic_logs.h): the buffers the weight-gradient launch will leave
+        # its partials in are workspace tensors with fixed names, so the struct can be built before the body runs
+        ws_ = lu.agent_ws(agent, dev)
+        N_ = c_arena_.n_nets
+        ttot_ = (engine.bf16_tiles_total(c_arena_) if c_arena_.shadow is not None
+                 else engine.wgrad_tiles_total(c_arena_))
+        gs.td_stats = ws_.get("cu.tdstats", (4,), zero=True)
+        ctx.deferred = _lib.DeferredLogs(
+            ws_.get("cu.c0.fparts", (N_ * 2,)).data_ptr(), N_, N_ * ttot_, ws_.get("cu.ss0", (N_ * ttot_,)).data_ptr(),
+            gs.td_stats.data_ptr(), lu.L_TD0, B, float(N_ if gs.shard is None else gs.n_critics), 0, gs.feed.ptr)
+        t_arena_ = kw["target_agent"].critics[0].arena(dev)
+        if (gs.late_word is not None and (c_arena_.shadow is None) == (t_arena_.shadow is None)
+                and t_arena_.params.numel() == c_arena_.params.numel()):
+            # late-bound Polyak: the weight-gradient launch carries the target arena and waits for the decision
+            ctx.late = gs.late_word.data_ptr()
+            ctx.late_target = t_arena_
+
+    gs.members = []   # the members' records: what a replay reads lives as long as the recording
+
+    def body():
+        logs_, dicts_ = _critic_update_eager(_records=gs.members, **kw)
+        assert not ctx.pending_begin, "deferred ssac_begin_update was never issued"
+        assert ctx.deferred_used == ctx.deferred_chain, "deferred log finalisation: chain / weight-gradient mismatch"
+        gs.deferred = ctx.deferred if ctx.deferred_used else None
+        gs.late_arenas = ((ctx.late_target, agent.critics[0].arena(dev))
+                          if (ctx.deferred_used and ctx.late_used) else None)
+        if not ctx.published:
+            check(lib.ssac_publish_logs(gs.logblk.data_ptr(), gs.feed.ptr, engine.stream()))
+        return logs_, dicts_
+    engine.CAPTURE = ctx
+    try:
+        if LAUNCH_MODE == "graph":
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logs, dicts = body()
+            graph.replay()
+        else:
+            # launch list: this call's launches run normally AND are recorded for the later calls
+            graph = _LaunchList()
+
+            def collective(fn):
+                graph.add_list(lib.ssac_record_end())
+                fn()
+                graph.parts.append(fn)
+                check(lib.ssac_record_begin())
+            ctx.collective = collective
+            check(lib.ssac_record_begin())
+            try:
+                logs, dicts = body()
+            finally:
+                handle = lib.ssac_record_end()
+            graph.add_list(handle)
+    finally:
+        engine.CAPTURE = None
+    gs.graph, gs.dicts = graph, dicts
+    base = gs.logblk.data_ptr()
+    gs.log_index = {k_: (v.data_ptr() - base) // 4 for k_, v in logs.items()}
+    gs.log_views = {}   # the 0-dim views handed out as log values, built once per ring slot (gs.views)
 
 
 def _loss_folds(n_rows):

@@ -68,7 +68,7 @@ DEFERRED_LOGS = True
 def flush_pending_logs(owner):
     """write the newest recorded update's log block to its ring slot now (owner: the recording's state object, which
     carries `pending` = that update's log-ring slot, and `deferred` = its ssac_deferred_logs struct)"""
-    slot_i = owner.__dict__.get("pending")
+    slot_i = owner.pending
     if slot_i is not None:
         owner.pending = None
         check(lib.ssac_deferred_logs_flush(C.byref(owner.deferred), slot_i, engine.stream()))
@@ -83,7 +83,7 @@ class LazyLog(torch.Tensor):
         for a in args:
             if isinstance(a, LazyLog):
                 owner = a.__dict__.get("_ssac_owner")
-                if owner is not None and owner.__dict__.get("pending") == a.__dict__.get("_ssac_slot"):
+                if owner is not None and owner.pending == a.__dict__.get("_ssac_slot"):
                     flush_pending_logs(owner)
         return super().__torch_function__(func, types, args, kwargs or {})
 

@@ -698,6 +698,167 @@ def test_recorded_updates_wrap_the_input_ring():
         assert a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2])
 
 
+def test_recorded_updates_change_replayer_in_the_middle_of_a_run():
+    """The shapes of test_recorded_updates_wrap_the_input_ring, but for calls 45-52 and 77-78 the C step
+    (ssac_step_run) is out of reach, so those calls replay through the Python path on the same record and hand back
+    to the C step afterwards.  The first window starts off an EVENT_EVERY boundary, crosses one and comes after the
+    input ring has wrapped once; the second is shorter than an event group.  Against 100 eager updates: same
+    parameters, same target parameters, same logs and replay indices at calls 40, 60 and 99, bit for bit."""
+    import copy
+    import math
+    import random
+    from itertools import chain
+
+    import torch
+    import super_sac_amd as ssa
+
+    n_upd, windows = 100, ((45, 52), (77, 78))
+
+    def run(recorded):
+        old = ssa.learning.USE_GRAPHS
+        ssa.learning.USE_GRAPHS = recorded
+        try:
+            torch.manual_seed(11); np.random.seed(11); random.seed(11)
+            dev = torch.device("cuda")
+            agent = ssa.Agent(act_space_size=3, encoder=ssa.nets.IdentityEncoder(11),
+                              actor_network_cls=ssa.nets.ContinuousStochasticActor,
+                              critic_network_cls=ssa.nets.ContinuousCritic, ensemble_size=1, num_critics=3,
+                              hidden_size=64, auto_rescale_targets=False, log_std_low=-5.0, log_std_high=2.0)
+            agent.to(dev)
+            target = copy.deepcopy(agent)
+            buf = ssa.replay.ReplayBuffer(4096, device=dev)
+            buf.load_experience(*synth.synth_transitions(1500, 11, 3, seed=9))
+            copt = torch.optim.Adam(chain(*(c.parameters() for c in agent.critics)), lr=3e-4)
+            eopt = torch.optim.Adam(agent.encoder.parameters(), lr=1e-4)
+            la = torch.Tensor([math.log(0.2)]).to(dev); la.requires_grad = True
+            aug = ssa.augmentations.AugmentationSequence([ssa.augmentations.IdentityAug(96)])
+            seen, taken = [], {}
+            for k in range(n_upd):
+                if recorded and any(k == first for first, _ in windows):
+                    fast = agent.__dict__["_ssac_fast"]
+                    taken = dict(fast)
+                    assert taken, "the fast C step was never reached"
+                    fast.clear()
+                logs, dicts = ssa.learning.critic_update(
+                    buffer=buf, agent=agent, target_agent=target, critic_optimizer=copt, encoder_optimizer=eopt,
+                    log_alphas=[la], batch_size=96, gamma=0.99, critic_clip=None, encoder_clip=None,
+                    target_critic_ensemble_n=2, weighted_bellman_temp=None, weight_type=None, pop=False,
+                    augmenter=aug, encoder_lambda=0, aug_mix=0.0, discrete=False, random_process=None,
+                    noise_clip=None, per=False, update_priorities=False, dr3_coeff=0.0)
+                if recorded and any(k == last for _, last in windows):
+                    assert not agent.__dict__["_ssac_fast"], "a second C step was built inside the window"
+                    agent.__dict__["_ssac_fast"].update(taken)   # the same objects
+                if k % 2 == 1:
+                    ssa.learning_utils.soft_update(target.critics[0], agent.critics[0], 0.01)
+                if k in (40, 60, 99):
+                    seen.append((float(logs["losses/critic_overall_loss"]), float(logs["td_targets/mean_td_target_0"]),
+                                 dicts[0]["priority_idxs"].copy()))
+            params = torch.cat([p.detach().flatten() for p in agent.critics[0].parameters()]).cpu().numpy()
+            tparams = torch.cat([p.detach().flatten() for p in target.critics[0].parameters()]).cpu().numpy()
+            if recorded:
+                record, = agent.__dict__["_ssac_graphs"].values()
+                step, = agent.__dict__["_ssac_fast"].values()
+                assert step is record.fast and step.gs is record
+                assert record.path == "fast"
+                assert record.k == n_upd - ssa.learning.GRAPH_WARMUP
+                # every call but the warm-up, the recording call and the two windows went through the C step
+                assert step.calls == n_upd - ssa.learning.GRAPH_WARMUP - 1 - sum(b - a + 1 for a, b in windows)
+            return params, tparams, seen
+        finally:
+            ssa.learning.USE_GRAPHS = old
+
+    pe, te, se = run(False)
+    pr, tr, sr = run(True)
+    assert np.array_equal(pe, pr) and np.array_equal(te, tr)
+    assert len(se) == len(sr) == 3
+    for a, b in zip(se, sr):
+        assert a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2])
+
+
+def test_recorded_updates_record_again_when_a_noise_hook_comes_and_goes():
+    """The shapes of test_recorded_updates_wrap_the_input_ring with a noise hook (a private generator behind rng.draw_normal /
+    rng.draw_normal_into) installed before call 43 and removed before call 59.  Each change makes the recorded run drop
+    its recording and record again -- at ring updates 40 and 56, both past FEED_SLOTS and on an EVENT_EVERY boundary, on
+    the same input ring -- and retires the C step built over the dropped launch lists; a new one serves the calls after.
+    Against eager updates under the same hook schedule: same parameters, target parameters, logs and replay indices."""
+    import copy
+    import math
+    import random
+    from itertools import chain
+
+    import torch
+    import super_sac_amd as ssa
+
+    n_upd, hook_on, hook_off = 100, 43, 59
+
+    def run(recorded):
+        old = ssa.learning.USE_GRAPHS, ssa.rng.draw_normal, ssa.rng.draw_normal_into
+        ssa.learning.USE_GRAPHS = recorded
+        try:
+            torch.manual_seed(11); np.random.seed(11); random.seed(11)
+            dev = torch.device("cuda")
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(77)
+            agent = ssa.Agent(act_space_size=3, encoder=ssa.nets.IdentityEncoder(11),
+                              actor_network_cls=ssa.nets.ContinuousStochasticActor,
+                              critic_network_cls=ssa.nets.ContinuousCritic, ensemble_size=1, num_critics=3,
+                              hidden_size=64, auto_rescale_targets=False, log_std_low=-5.0, log_std_high=2.0)
+            agent.to(dev)
+            target = copy.deepcopy(agent)
+            buf = ssa.replay.ReplayBuffer(4096, device=dev)
+            buf.load_experience(*synth.synth_transitions(1500, 11, 3, seed=9))
+            copt = torch.optim.Adam(chain(*(c.parameters() for c in agent.critics)), lr=3e-4)
+            eopt = torch.optim.Adam(agent.encoder.parameters(), lr=1e-4)
+            la = torch.Tensor([math.log(0.2)]).to(dev); la.requires_grad = True
+            aug = ssa.augmentations.AugmentationSequence([ssa.augmentations.IdentityAug(96)])
+            seen, steps = [], []
+            for k in range(n_upd):
+                if k == hook_on:
+                    ssa.rng.draw_normal = lambda shape, device: torch.randn(*shape, device=device, generator=gen)
+                    ssa.rng.draw_normal_into = lambda dst: dst.normal_(generator=gen)
+                if k == hook_off:
+                    ssa.rng.draw_normal, ssa.rng.draw_normal_into = old[1:]
+                logs, dicts = ssa.learning.critic_update(
+                    buffer=buf, agent=agent, target_agent=target, critic_optimizer=copt, encoder_optimizer=eopt,
+                    log_alphas=[la], batch_size=96, gamma=0.99, critic_clip=None, encoder_clip=None,
+                    target_critic_ensemble_n=2, weighted_bellman_temp=None, weight_type=None, pop=False,
+                    augmenter=aug, encoder_lambda=0, aug_mix=0.0, discrete=False, random_process=None,
+                    noise_clip=None, per=False, update_priorities=False, dr3_coeff=0.0)
+                if k % 2 == 1:
+                    ssa.learning_utils.soft_update(target.critics[0], agent.critics[0], 0.01)
+                if k in (40, 43, 50, 59, 99):
+                    seen.append((float(logs["losses/critic_overall_loss"]), float(logs["td_targets/mean_td_target_0"]),
+                                 dicts[0]["priority_idxs"].copy()))
+                if recorded and k in (hook_on - 1, hook_on, hook_off - 1, hook_off, n_upd - 1):
+                    record, = agent.__dict__["_ssac_graphs"].values()
+                    steps.append((record.fast, record.in_kernel_noise, record.k))
+            params = torch.cat([p.detach().flatten() for p in agent.critics[0].parameters()]).cpu().numpy()
+            tparams = torch.cat([p.detach().flatten() for p in target.critics[0].parameters()]).cpu().numpy()
+            if recorded:
+                warm = ssa.learning.GRAPH_WARMUP
+                # the ring goes on counting over both re-recordings: no update starts again from slot 0
+                assert [s_[2] for s_ in steps] == [hook_on - warm, hook_on - warm + 1, hook_off - warm, hook_off - warm + 1,
+                                                  n_upd - warm]
+                assert [s_[1] for s_ in steps] == [True, False, False, True, True]
+                # three C steps, one per recording; each is retired with its recording and serves only its own calls
+                first, second, third = steps[0][0], steps[1][0], steps[3][0]
+                assert steps[2][0] is second and steps[4][0] is third and len({id(first), id(second), id(third)}) == 3
+                assert first.calls == hook_on - warm - 1          # calls 4 .. 42 (+ 0: call 43 finds the hook first)
+                assert second.calls == hook_off - hook_on - 1     # calls 44 .. 58
+                assert third.calls == n_upd - hook_off - 1        # calls 60 .. 99
+                assert record.path == "fast" and list(agent.__dict__["_ssac_fast"].values()) == [third]
+            return params, tparams, seen
+        finally:
+            ssa.learning.USE_GRAPHS, ssa.rng.draw_normal, ssa.rng.draw_normal_into = old
+
+    pe, te, se = run(False)
+    pr, tr, sr = run(True)
+    assert np.array_equal(pe, pr) and np.array_equal(te, tr)
+    assert len(se) == len(sr) == 5
+    for a, b in zip(se, sr):
+        assert a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2])
+
+
 def test_packed_push_and_n_step_fold_match_the_reference_storage():
     """buffer.push through the packed single-copy path (ring wrap-around, batched and single transitions, uint8
     images) against a plain numpy ring (ReplayBufferStorage.add, replay.py:48-60), and NStepFolder against the
