@@ -57,6 +57,13 @@ int ssac_chain_form(int form);
 int ssac_chain_lean(int on);
 /* which of the two the LAST ssac_chain_update launch took: 1 lean, 0 general, -1 no launch yet. */
 int ssac_chain_lean_taken(void);
+/* default 1: the merged weight-gradient launch takes its fixed-shape form whenever the launch qualifies -- 64 x 64 tiles
+ * with four K-groups on the lean kernel, Adam mode, the loss fold on, hidden 256, one head output, an input of 4 .. 32
+ * columns, the whole ensemble in one resident round, 16-byte aligned arenas, every gradient-norm slot present; 0 = never
+ * (the general instantiations).  Weight decay, PopArt and per-row weights are carried by both.  Bit-identical results. */
+int ssac_wgrad_fixed(int on);
+/* which form the LAST merged weight-gradient launch took: 1 fixed-shape, 0 any other, -1 no launch yet. */
+int ssac_wgrad_fixed_taken(void);
 /* large-batch form of ssac_bf16_mlp3_fwd: 1 (default) = the register-chained kernel where it applies, 0 = the streaming
  * kernel everywhere.  Same operands, same rounding points. */
 int ssac_bf16_fwd_form(int form);

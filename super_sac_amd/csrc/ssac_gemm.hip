@@ -263,11 +263,17 @@ struct LateTau { bool on; uint32_t bits; };
 // but the loop body was ~700 instructions long and its registers were allocated for the worst path.  One instantiation
 // of this body per KERNEL (a second one inside the same kernel makes the compiler copy the argument block to scratch),
 // hence the kernel carries the flag.
-template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false>
+// FIXED (the fixed-shape form of the merged weight-gradient launch, wgrad_fixed_kernel below; 0 = off): the caller hands in
+// a GemmArgs it BUILT from constants -- hidden 256, leading dimensions, strides, no ids, no split K, no eager row scale --
+// so everything derived from them folds at compile time; the flag adds the facts the values alone cannot tell: 1 = an fc2
+// tile (256 x 256: every column block exists, the 16-byte optimizer form, no bias gradient), 2 = an fc1 tile (one column
+// block of at most 32 columns: the waves of the right half never multiply); both: gradient-norm slots are present.
+template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false, int FIXED = 0>
 __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int bx, int by, int bz,
                                               float *late_rs, const LossFoldArgs &lf, int lf_mode,
                                               const LogFoldArgs &fold, int &last,
                                               const LateTau &lt = LateTau{false, 0u}) {
+    GSTAMP(13);   // (the role's first instruction: what lies between it and stamp 0 is the tile's front)
     const int tid_all = threadIdx.x;
     // (K-group and wave index are the same in every lane of a wave: said so explicitly, everything derived from them --
     // the tile quadrant, "this wave sums the bias", "this wave's columns do not exist" -- is a scalar branch instead of
@@ -295,7 +301,9 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     const int li = lane & 31, lh = lane >> 5;
     const int e = bz;
     const int m0 = by * BM, n0 = bx * BN;
-    const bool dead_cols = TN_ROT && (n0 + wn * 32) >= g.N;   // (wave-uniform) this wave's 32 columns lie beyond the matrix
+    static_assert(FIXED == 0 || (VECONLY && EPI == EPI_ADAM && KS == 4), "the fixed-shape form is the lean Adam kernel with four K-groups");
+    // (wave-uniform) this wave's 32 columns lie beyond the matrix
+    const bool dead_cols = FIXED == 1 ? false : FIXED == 2 ? wn != 0 : (TN_ROT && (n0 + wn * 32) >= g.N);
 
     const float *A = g.A + batch_off(g.ids, g.idsA, e, g.sA);
     const float *B = g.B + batch_off(g.ids, g.idsB, e, g.sB);
@@ -366,7 +374,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     //      with a round trip to HBM / the Infinity Cache: 16-byte form, one float4 per thread (KS = 4) only.
     constexpr int NT_ALL_ = NTHREADS * KS;
     constexpr bool PREFETCH_OPT = EPI == EPI_ADAM && (BM * BN / 4) / NT_ALL_ == 1;
-    const bool vecC = (EPI == EPI_ADAM || EPI == EPI_GRAD) && (g.N & 3) == 0 && (g.ldc & 3) == 0 && (coff & 3) == 0 &&
+    const bool vecC = FIXED == 1 ? true : (EPI == EPI_ADAM || EPI == EPI_GRAD) && (g.N & 3) == 0 && (g.ldc & 3) == 0 && (coff & 3) == 0 &&
                       ((((uintptr_t)g.C | (uintptr_t)g.am | (uintptr_t)g.av | (uintptr_t)g.tw | (uintptr_t)g.gw) & 15) == 0);
     const bool pol_ = g.tw != nullptr && (!lt.on || lt.bits != 0u);
     f4 pf_p, pf_m, pf_v, pf_t;
@@ -516,7 +524,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         // lanes 1..3 of the same store instruction (one slot per 32 x 32 block, above); lane 0 then draws the arrival ticket of the
         // folded logs (its wave's stores drained first: log_fold_arrive).
         auto sumsq_finish = [&]() {
-            if (!(g.sumsq && (tid_all >> 6) == 4 * KS - 1)) return;
+            if (!((FIXED || g.sumsq) && (tid_all >> 6) == 4 * KS - 1)) return;
             float tot = lane < 4 * KS ? red[lane] : 0.0f;
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);   // (4 KS <= 16 partials in lanes 0..15)
@@ -577,7 +585,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                     for (int c = 0; c < 4; ++c) ss += g4[j][c] * g4[j][c];
                 }
             if (bias_thr_) ss += bsum_ * bsum_;
-            if (g.sumsq) {
+            if (FIXED || g.sumsq) {
                 ss = wave_sum(ss);
                 GSTAMP(10);
                 lds_barrier();  // red[] (bias partials) and the partial tiles have been consumed
@@ -663,7 +671,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         for (int j = 0; j < PER; ++j)
             if (ok[j]) ss += gval[j] * gval[j];
         if (bias_thr) ss += bsum * bsum;
-        if (g.sumsq) {
+        if (FIXED || g.sumsq) {
             ss = wave_sum(ss);
             __syncthreads();  // red[] (bias partials) has been consumed
             if (lane == 0) red[tid_all >> 6] = ss;
@@ -873,6 +881,137 @@ __global__ __launch_bounds__(NTHREADS *KS) void ens_gemm_pair_kernel(GemmPair p)
     }
 #ifdef SSAC_LAB
     if (p.tl && blockIdx.x < 512) {   // (the stamp buffer holds 512 workgroups per launch)
+        __syncthreads();
+        if (threadIdx.x == 0) p.tl[1024 + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// FIXED-SHAPE FORM of the merged weight-gradient launch: the critic update of hidden-256, single-output critics over an
+// input of at most 32 columns (the headline's class of launches; conditions: wgrad_fixed_ok).  Same workgroup classes,
+// same body, same arithmetic and order of every sum as ens_gemm_pair_kernel<TN, adam, 4, lean> -- but a tile does not
+// read its shape from the argument block: each role BUILDS its GemmArgs / HeadWgradArgs from constants and the few words
+// that really vary (operand and arena bases, row count, input width), so the strides, tile counts, id indirection, split
+// K, eager row scale, the dword epilogue of fc2 and the multi-round loss-fold table are not compiled into it, and an fc2
+// tile starts from a handful of scalar loads instead of dependent groups of them spread over its front.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int FX_H = 256;                       // hidden width
+constexpr int FX_GRID = FX_H / BM;              // 4: tile rows of both problems, tile columns of fc2, head workgroups per net
+constexpr int FX_TILES2 = FX_GRID * FX_GRID;    // fc2 tiles per net
+
+// The compact argument block: what the fixed form reads and nothing else.  An fc2 tile's words come first and together
+// (its two operands, the arena bases, the control block, the W3 snapshot: one 64-byte scalar load), the layer offsets are
+// functions of in_dim, the tile counts of n_nets: under 0x1d0 bytes.  GemmPair's two GemmArgs + HeadWgradArgs hold the same
+// facts three times and reach past offset 0x460.
+struct WgradFixedArgs {
+    const float *A2, *H1;                  // fc2: dz2u (or h2, with a_sign_w) and h1, (n_nets x n_rows x 256) each
+    float *params, *am, *av, *tw;          // arena bases: parameters, Adam moments, Polyak target (null: none)
+    const ssac_adam_ctl *ctl;
+    const float *a_sign_w;                 // != null: A2 is h2 and dz2u is rebuilt from its sign (GemmArgs::a_sign_w)
+    float *sumsq1; int64_t net_stride, sumsq_stride;
+    int n_rows, in_dim; float tau; int xcd;
+    int tiles0, tiles01, head_total, xcd_mix, td_wg;
+    int ldx; int64_t x_stride;             // fc1's B: the critics' input rows
+    const float *DZ1, *X, *H2;
+    float *sumsq0, *sumsq2;
+    const uint32_t *late_word;
+    long long *tl, *dbg;
+    LossFoldArgs lf;
+    LogFoldArgs fold;
+};
+struct FixedOffsets { int64_t b1, w2, b2, w3, b3; };   // ssac_mlp_layout(in_dim, 256, 1); w1 = 0
+__host__ __device__ __forceinline__ FixedOffsets wgrad_fixed_offsets(int in_dim) {
+    FixedOffsets o;
+    o.b1 = (int64_t)FX_H * in_dim; o.w2 = o.b1 + FX_H; o.b2 = o.w2 + FX_H * FX_H; o.w3 = o.b2 + FX_H; o.b3 = o.w3 + FX_H;
+    return o;
+}
+// ROLE 1: the fc2 problem (dW2 = dz2^T h1), ROLE 2: fc1 (dW1 = dz1^T x)
+template <int ROLE>
+__device__ __forceinline__ GemmArgs wgrad_fixed_tile(const WgradFixedArgs &p) {
+    const FixedOffsets o = wgrad_fixed_offsets(p.in_dim);
+    const int64_t ow = ROLE == 1 ? o.w2 : 0, ob = ROLE == 1 ? o.b2 : o.b1;
+    GemmArgs g{};   // (ids, bias, mask, gradient outputs, row scale, Ktot: null / 0)
+    g.A = ROLE == 1 ? p.A2 : p.DZ1; g.lda = FX_H; g.sA = (int64_t)p.n_rows * FX_H;
+    g.B = ROLE == 1 ? p.H1 : p.X; g.ldb = ROLE == 1 ? (int64_t)FX_H : (int64_t)p.ldx; g.sB = ROLE == 1 ? (int64_t)p.n_rows * FX_H : p.x_stride;
+    g.C = p.params + ow; g.ldc = ROLE == 1 ? FX_H : p.in_dim; g.sC = p.net_stride;
+    g.M = FX_H; g.N = ROLE == 1 ? FX_H : p.in_dim; g.K = p.n_rows;
+    g.am = p.am + ow; g.av = p.av + ow; g.pb = p.params + ob; g.bm = p.am + ob; g.bv = p.av + ob;
+    g.tw = p.tw ? p.tw + ow : nullptr; g.tb = p.tw ? p.tw + ob : nullptr;
+    g.tau = p.tau; g.ctl = p.ctl; g.sumsq = ROLE == 1 ? p.sumsq1 : p.sumsq0; g.sumsq_stride = p.sumsq_stride;
+    g.dbg = ROLE == 1 ? p.dbg : nullptr;
+    g.grid_x = ROLE == 1 ? FX_GRID : 1; g.grid_y = FX_GRID;
+    g.a_sign_w = ROLE == 1 ? p.a_sign_w : nullptr;
+    g.no_bias = ROLE == 1 ? 1 : 0;   // (fc2's bias gradient: the head workgroups, HeadWgradArgs::with_b2)
+    return g;
+}
+__device__ __forceinline__ HeadWgradArgs wgrad_fixed_head(const WgradFixedArgs &p) {
+    const FixedOffsets o = wgrad_fixed_offsets(p.in_dim);
+    // (DQ: never read -- the head takes dL/dq from the folded table -- but left a real pointer)
+    return HeadWgradArgs{p.params, p.net_stride, FX_H, 1, o.w3, o.b3, nullptr, p.H2, p.H2, p.n_rows, p.am, p.av, p.ctl, nullptr,
+                         p.sumsq2, p.sumsq_stride, p.tw, p.tau, 1, o.b2};
+}
+
+__global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArgs p) {
+    constexpr int KS = 4;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    SSAC_LAB_ONLY(if (p.tl && threadIdx.x == 0 && blockIdx.x < 512) p.tl[1024 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();)
+    // (workgroup order: as in ens_gemm_pair_kernel -- the TD workgroup behind the others keeps its own id)
+    const int n_main = p.tiles01 + p.head_total;
+    int bid = (int)blockIdx.x < n_main ? ssac_xcd_contiguous(blockIdx.x, n_main, p.xcd) : (int)blockIdx.x;
+    if (p.xcd_mix && (int)blockIdx.x < n_main) {
+        const int x = blockIdx.x & 7, slot = blockIdx.x >> 3;
+        const int a8 = p.tiles0 >> 3, f8 = (p.tiles01 - p.tiles0) >> 3, h8 = p.head_total >> 3;
+        bid = slot < a8 ? x * a8 + slot
+                        : (slot < a8 + f8 ? p.tiles0 + x * f8 + (slot - a8) : p.tiles01 + x * h8 + (slot - a8 - f8));
+    }
+    float *tab = lds + KS * (4 * TILE_FLOATS) + 64 * KS;  // folded loss gradient: [n_rows] row scales, then scratch
+    const LateTau lt{p.late_word != nullptr, p.late_word ? *p.late_word : 0u};
+    int last = 0;
+    bool drawn = false;
+    if (p.td_wg && bid == n_main) {
+        // the TD targets and their statistics (the nets' loss terms: the first head workgroup of every net)
+        loss_fold_table(p.lf, 0, tab, false, tab + p.lf.n_rows, true);
+        __syncthreads();
+        if ((p.fold.done && p.fold.td_logs) || p.fold.deferred_stats)
+            log_fold_td_stats(p.fold, p.lf.tds, tab + p.lf.n_rows);
+    } else if (bid >= p.tiles01) {  // head-layer weight gradient (+ fc2's bias gradient) + Adam
+        const int L = bid - p.tiles01;
+        const int e = L / FX_GRID, hx = L % FX_GRID;
+        loss_fold_table(p.lf, e, tab, hx == 0, tab + p.lf.n_rows, false);
+        __syncthreads();
+        const HeadWgradArgs head = wgrad_fixed_head(p);
+        bool hpol = head.target != nullptr;
+        float htau = head.tau;
+        if (lt.on) {
+            hpol = hpol && lt.bits != 0u;
+            htau = __uint_as_float(lt.bits);
+        }
+        head_wgrad_body<4 * KS>(head, lds, hx, e, tab, hpol, htau, KS * 4 * TILE_FLOATS + 64 * KS);
+    } else if (bid < p.tiles0) {
+        const GemmArgs g = wgrad_fixed_tile<1>(p);
+        const int bz = bid / FX_TILES2, rem = bid % FX_TILES2;
+        ens_gemm_body<false, false, EPI_ADAM, KS, true, 1>(g, lds, rem % FX_GRID, rem / FX_GRID, bz, tab, p.lf, 1, p.fold, last, lt);
+        drawn = true;
+    } else {
+        const GemmArgs g = wgrad_fixed_tile<2>(p);
+        const int L = bid - p.tiles0;
+        ens_gemm_body<false, false, EPI_ADAM, KS, true, 2>(g, lds, 0, L % FX_GRID, L / FX_GRID, tab, p.lf, 1, p.fold, last, lt);
+        drawn = true;
+    }
+    if (p.fold.done) {
+        // (as in ens_gemm_pair_kernel: a GEMM tile's ticket was drawn by lane 0 of its last wave, the others draw it here)
+        float *flag = lds + KS * (4 * TILE_FLOATS);
+        __syncthreads();
+        if (threadIdx.x == (drawn ? (4 * KS - 1) * 64 : 0))
+            flag[0] = (drawn ? last != 0 : log_fold_arrive(p.fold, gridDim.x)) ? 1.0f : 0.0f;
+        __syncthreads();
+        if (flag[0] != 0.0f && threadIdx.x < 64) log_fold_finish(p.fold);
+    } else if (p.fold.deferred_stats && p.fold.feed && blockIdx.x == 0 && threadIdx.x == 0) {
+        p.fold.feed->tick += 1;   // deferred finalisation: the update is over for the input ring (no reader in this launch)
+    }
+#ifdef SSAC_LAB
+    if (p.tl && blockIdx.x < 512) {
         __syncthreads();
         if (threadIdx.x == 0) p.tl[1024 + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
     }
@@ -1272,6 +1411,51 @@ bool lean_ok(const GemmArgs &g) {
            (int64_t)(g.K + 1) * g.ldb < (1LL << 31);
 }
 
+int g_wgrad_fixed = 1;          // ssac_wgrad_fixed: 0 = the merged launch never takes its fixed-shape form
+int g_wgrad_fixed_taken = -1;   // ssac_wgrad_fixed_taken: form of the last merged weight-gradient launch (1 fixed, 0 any other, -1 none yet)
+
+// May a launch of the lean kernel with four K-groups and the Adam epilogue (p filled in by launch_pair_ks) take the
+// fixed-shape form?  Everything wgrad_fixed_kernel compiles in as a constant or leaves out is checked here.
+bool wgrad_fixed_ok(const GemmPair &p, int n_nets, int total) {
+    const GemmArgs &a = p.g0, &b = p.g1;
+    const HeadWgradArgs &h = p.head;
+    auto al16 = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
+    return a.M == FX_H && a.N == FX_H && a.lda == FX_H && a.ldb == FX_H && a.ldc == FX_H &&         // fc2: 256 x 256, dense
+           b.M == FX_H && b.lda == FX_H && b.N >= 4 && b.N <= 32 && b.ldc == b.N &&                 // fc1: one column block
+           a.K == b.K && a.sA == (int64_t)a.K * FX_H && a.sB == a.sA && b.sA == a.sA && a.sC == b.sC &&
+           !a.ids && !b.ids && !a.rowscale && !b.rowscale && !b.a_sign_w &&                          // whole ensemble, late row scales
+           a.no_bias == 1 && b.no_bias == 0 && a.ctl && a.ctl == b.ctl && a.tau == b.tau && (a.tw != nullptr) == (b.tw != nullptr) &&
+           (a.sC & 3) == 0 && al16(a.C) && al16(a.am) && al16(a.av) && al16(a.tw) &&                // fc2: the 16-byte optimizer form
+           a.sumsq && b.sumsq && h.sumsq && a.sumsq_stride == b.sumsq_stride &&
+           p.lf.q && p.stats_in_head == 1 && p.lf_nets == 0 && !p.fold.actor &&                     // loss fold on, one-step tables in the head
+           p.head_grid_x == FX_GRID && h.hidden == FX_H && h.out_dim == 1 && !h.ids && !h.grads && h.with_b2 == 1 &&
+           p.tiles0 == FX_TILES2 * n_nets && p.tiles01 == (FX_TILES2 + FX_GRID) * n_nets && p.head_total == FX_GRID * n_nets &&
+           total <= 256 &&                                                                           // one resident round
+           // ... and the three views of the arenas are ONE arena each, laid out by ssac_mlp_layout (the compact block keeps the bases)
+           [&] {
+               const FixedOffsets o = wgrad_fixed_offsets(b.N);
+               auto at = [](const float *base, int64_t off, const float *q) { return base ? q == base + off : q == nullptr; };
+               return h.off_w == o.w3 && h.off_b == o.b3 && h.off_b2 == o.b2 && h.net_stride == a.sC && h.n_rows == a.K &&
+                      h.ctl == a.ctl && h.tau == a.tau && h.sumsq_stride == a.sumsq_stride &&
+                      at(h.params, o.w2, a.C) && at(h.params, 0, b.C) && at(h.params, o.b2, a.pb) && at(h.params, o.b1, b.pb) &&
+                      at(h.am, o.w2, a.am) && at(h.am, 0, b.am) && at(h.am, o.b2, a.bm) && at(h.am, o.b1, b.bm) &&
+                      at(h.av, o.w2, a.av) && at(h.av, 0, b.av) && at(h.av, o.b2, a.bv) && at(h.av, o.b1, b.bv) &&
+                      at(h.target, o.w2, a.tw) && at(h.target, 0, b.tw) && at(h.target, o.b2, a.tb) && at(h.target, o.b1, b.tb);
+           }();
+}
+
+WgradFixedArgs wgrad_fixed_args(const GemmPair &p) {
+    WgradFixedArgs f{};
+    f.A2 = p.g0.A; f.H1 = p.g0.B; f.params = p.head.params; f.am = p.head.am; f.av = p.head.av; f.tw = p.head.target;
+    f.ctl = p.g0.ctl; f.a_sign_w = p.g0.a_sign_w; f.sumsq1 = p.g0.sumsq; f.net_stride = p.g0.sC; f.sumsq_stride = p.g0.sumsq_stride;
+    f.n_rows = p.g0.K; f.in_dim = p.g1.N; f.tau = p.g0.tau; f.xcd = p.xcd;
+    f.tiles0 = p.tiles0; f.tiles01 = p.tiles01; f.head_total = p.head_total; f.xcd_mix = p.xcd_mix; f.td_wg = p.td_wg;
+    f.ldx = (int)p.g1.ldb; f.x_stride = p.g1.sB; f.DZ1 = p.g1.A; f.X = p.g1.B; f.H2 = p.head.H2;
+    f.sumsq0 = p.g1.sumsq; f.sumsq2 = p.head.sumsq; f.late_word = p.late_word; f.tl = p.tl; f.dbg = p.g0.dbg;
+    f.lf = p.lf; f.fold = p.fold;
+    return f;
+}
+
 template <bool A_KC, bool B_KC, int EPI, int KS>
 int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
     static bool raised = false;
@@ -1297,6 +1481,16 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
     p.stats_in_head = (p.lf.q && p.head_total > 0) ? 1 : 0;
     p.lf_nets = (!p.stats_in_head && p.td_wg && p.tiles01 + p.head_total + 1 <= 256) ? batch0 : 0;
     const int total = p.tiles01 + p.head_total + p.td_wg;
+    if constexpr (TN_ && EPI == EPI_ADAM && KS == 4) {
+        // the fixed-shape form (wgrad_fixed_kernel): per launch, from what the launch itself says
+        if (lean && g_wgrad_fixed && wgrad_fixed_ok(p, batch0, total)) {
+            static bool raised_fixed = false;
+            if (ssac_raise_lds(raised_fixed, PAIR_LDS_MAX, "wgrad_fixed", wgrad_fixed_kernel)) return 1;
+            SSAC_LAUNCH(wgrad_fixed_kernel, dim3(total), dim3(NTHREADS * KS), lds, st, wgrad_fixed_args(p));
+            g_wgrad_fixed_taken = 1;
+            return ssac_check_launch("wgrad_fixed");
+        }
+    }
     if constexpr (TN_) {
         if (lean) {
             SSAC_LAUNCH((ens_gemm_pair_kernel<A_KC, B_KC, EPI, KS, true>), dim3(total), dim3(NTHREADS * KS), lds, st, p);
@@ -1426,6 +1620,14 @@ extern "C" int ssac_wgrad_variant(int variant) {
     g_wgrad_variant = variant;
     return 0;
 }
+
+// default 1: the merged weight-gradient launch takes its fixed-shape form (wgrad_fixed_kernel) whenever the launch
+// qualifies; 0 = never.  Bit-identical results (tests/test_hip_wgrad_fixed.py).
+extern "C" int ssac_wgrad_fixed(int on) {
+    g_wgrad_fixed = on ? 1 : 0;
+    return 0;
+}
+extern "C" int ssac_wgrad_fixed_taken(void) { return g_wgrad_fixed_taken; }
 
 extern "C" int64_t ssac_mlp_layout(int in_dim, int hidden, int out_dim, int64_t off[6]) {
     int64_t o = 0;
@@ -1594,6 +1796,7 @@ static int wgrad_merged(const ssac_mlp *nets, const int32_t *net_ids, int n_sel,
     if (n_sel < 0 || n_sel > SSAC_MAX_NETS) return ssac_fail("ssac_mlp_wgrad_fc12: n_sel out of range");
     if (!grads && (!adam_m || !adam_v || !ctl)) return ssac_fail("ssac_mlp_wgrad_fc12: Adam state missing");
     if (n_sel == 0 || n_rows <= 0) return 0;
+    g_wgrad_fixed_taken = 0;   // (launch_pair_ks says otherwise)
     const int H = nets->hidden;
     GemmPair p{};
     int64_t off[6];

@@ -1,6 +1,7 @@
 """(needs the LAB build of the library: ./build.sh --lab)
 s_memtime phase stamps inside the fp32 chained launch and the merged weight-gradient launch (eager launches of the
-real update at the headline shape; tile 0 of each role)       python tools/fp32_phases.py [B] [N]"""
+real update at the headline shape; tile 0 of each role)       python tools/fp32_phases.py [B] [N] [fixed]
+fixed: 0 = the weight-gradient launch keeps its general kernel (ssac_wgrad_fixed), default 1"""
 import os, sys
 os.environ.setdefault("SSAC_LAB_BUILD", "1")   # the lab library (./build.sh --lab -> libssac_hip_lab.so)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +14,8 @@ import super_sac_amd as ssa
 B = int(args[0]) if args else 512
 N = int(args[1]) if len(args) > 1 else 10
 ssa.learning.USE_GRAPHS = False
+if len(args) > 2:
+    ssa._lib.check(ssa._lib.lib.ssac_wgrad_fixed(int(args[2])))
 critic, _ = bc.build(17, 6, B, N, 2)
 for _ in range(5):
     critic()
@@ -35,6 +38,8 @@ row("target pass ", t, 16, names)
 print("actor start -> target pass end:", t[23] - t[0])
 row("critic WG   ", t, 32, names + ["loss", "head-bwd", "dgrad", "dz1-store"])
 row("wgrad tile 0", g, 0, ["operand issue + loss fold + first chunk", "K loop", "partials -> LDS", "adam epilogue"])
+print("wgrad tile 0 front (the role's first instruction -> stamp 0: argument words, addresses, the L2 touches):", g[0] - g[13],
+      " tile in all", g[4] - g[13], " form taken (1 fixed-shape):", ssa._lib.lib.ssac_wgrad_fixed_taken())
 print("wgrad tile 0 prologue (serialised by the debug stamps): first operand chunk", g[5] - g[0], " loss fold (pre)", g[6] - g[5],
       " LDS stores + second chunk", g[7] - g[6], " barrier + first fragment reads", g[1] - g[7])
 print("wgrad tile 0 epilogue: partial sums from LDS", g[8] - g[3], " gradient-norm partial (2 barriers)", g[9] - g[8], " Adam + stores issued", g[4] - g[9])
