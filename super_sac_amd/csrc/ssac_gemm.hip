@@ -302,6 +302,10 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     const int e = bz;
     const int m0 = by * BM, n0 = bx * BN;
     static_assert(FIXED == 0 || (VECONLY && EPI == EPI_ADAM && KS == 4), "the fixed-shape form is the lean Adam kernel with four K-groups");
+    // LEAN_HANDOFF: the fixed form's order of work behind the K loop (profiles/wgrad_handoff.md): partials parked in the
+    // free staging buffer with no barrier in front, the optimizer stores issued next, the gradient norm's wave partials
+    // (LDS words of their own, one barrier) behind them.  The general kernels keep the hand-off they had.
+    constexpr bool LEAN_HANDOFF = FIXED != 0;
     // (wave-uniform) this wave's 32 columns lie beyond the matrix
     const bool dead_cols = FIXED == 1 ? false : FIXED == 2 ? wn != 0 : (TN_ROT && (n0 + wn * 32) >= g.N);
 
@@ -378,6 +382,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                       ((((uintptr_t)g.C | (uintptr_t)g.am | (uintptr_t)g.av | (uintptr_t)g.tw | (uintptr_t)g.gw) & 15) == 0);
     const bool pol_ = g.tw != nullptr && (!lt.on || lt.bits != 0u);
     f4 pf_p, pf_m, pf_v, pf_t;
+    ssac_adam_ctl pf_ctl;   // (fixed form: the control block travels with the optimizer state)
     bool pf_done = false;
     auto opt_prefetch = [&]() {
         if (!vecC) return;
@@ -482,6 +487,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         // optimizer state takes their place (inside the loop the two live ranges would have overlapped)
         rd(f1a, f1b, ((iters - 1) & 1) ? buf1 : buf0, 1);
         if (PREFETCH_OPT) opt_prefetch();
+        if constexpr (LEAN_HANDOFF) pf_ctl = *g.ctl;   // (its epilogue no longer opens with work that would hide this load)
         mm(f0a, f0b);
         mm(f1a, f1b);
     }
@@ -495,12 +501,27 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         // a fixed order -> deterministic) by thread idx % (256*KS), so the optimizer's three loads
         // and three stores per element are spread over 4*KS waves and issued as independent batches
         // instead of one latency-bound chain per accumulator register.
+        // Fixed form: the partials go to the staging buffer that does NOT hold the last chunk.  Chunk it lives in buffer
+        // it & 1, so the last one is in buffer (iters - 1) & 1; the other one was last read in front of the K loop's final
+        // barrier, which every wave has passed by now (a single iteration never touched it).  So a wave parks as soon as
+        // its own last MFMA retires, with no barrier in front, while slower waves of its K-group still read the last
+        // chunk.  A staging buffer is [A tile | B tile] = 2 TILE_FLOATS >= 64 x 64 floats.
+        // (the bias partials: red[] is no staging buffer, nothing reads or writes it before this point)
+        // The general kernels park in buffer 0 behind a barrier of their own.
         float *mine = lds + kg * (4 * TILE_FLOATS);
-        lds_barrier();   // (LDS hand-offs only: the prefetched optimizer state stays in flight)
+        const float *parked = lds;   // K-group 0's partial tile, the others 4 TILE_FLOATS apart
+        if constexpr (LEAN_HANDOFF) {
+            const int park = (iters & 1) ? 2 * TILE_FLOATS : 0;   // (uniform) odd: the last chunk is in buf0
+            mine += park;
+            parked += park;
+        } else {
+            lds_barrier();   // (LDS hand-offs only: the prefetched optimizer state stays in flight)
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             mine[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + wn * 32 + li] = acc[r];
         if (bias_wave && lh == 0) red[kg * 64 + wm * 32 + li] = bias_acc;
+        GSTAMP(14);   // (this wave's partials are on their way to LDS)
         // The arrival ticket of the folded logs is drawn by the LAST wave (sumsq_finish), the net's loss partials were stored
         // by wave 0 at the front (loss_fold_table): wave 0 drains its stores in front of THIS barrier, which the last wave
         // passes before it draws -- the order no longer rests on the K loop's waits (by now only the prefetched optimizer
@@ -511,7 +532,8 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         constexpr int NT_ALL = NTHREADS * KS;
         constexpr int PER = (BM * BN) / NT_ALL;  // 16 / KS elements per thread
         ssac_adam_ctl ctl;
-        if (EPI == EPI_ADAM) ctl = *g.ctl;
+        if constexpr (LEAN_HANDOFF) ctl = pf_ctl;
+        else if (EPI == EPI_ADAM) ctl = *g.ctl;
         // target update in this epilogue: always (static tau) for eager callers, or only when this update's Polyak
         // request is in the ring tail (late-bound)
         const bool pol = g.tw != nullptr && (!lt.on || lt.bits != 0u);
@@ -523,9 +545,22 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         // partials (deterministic), the slot of the tile's first 32 x 32 block takes the sum and the siblings are zeroed by
         // lanes 1..3 of the same store instruction (one slot per 32 x 32 block, above); lane 0 then draws the arrival ticket of the
         // folded logs (its wave's stores drained first: log_fold_arrive).
+        // The wave partials meet in red[0..15] in the general kernels: that aliases the bias partials, so a barrier stands in
+        // front of the write as well as behind it.  The fixed form gives them 16 floats of their own behind red[] -- write,
+        // ONE barrier, sum -- and takes all of it BEHIND the optimizer stores (`sumsq_handoff`): the norm is a log value
+        // there (EPI_ADAM never clips), and the stores' drain, which every tile pays before it can end, runs under the
+        // barrier instead of behind it.  The last wave still sums behind its own stores and then draws the ticket.
+        float *wsum = red + 64 * KS;   // (fixed form only: wgrad_fixed_kernel's FX_WSUM floats)
+        auto sumsq_handoff = [&](float ss_) {
+            GSTAMP(11);
+            if (lane == 0) wsum[tid_all >> 6] = ss_;
+            lds_barrier();
+            GSTAMP(12);
+        };
         auto sumsq_finish = [&]() {
             if (!((FIXED || g.sumsq) && (tid_all >> 6) == 4 * KS - 1)) return;
             float tot = lane < 4 * KS ? red[lane] : 0.0f;
+            if constexpr (LEAN_HANDOFF) tot = lane < 4 * KS ? wsum[lane] : 0.0f;
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);   // (4 KS <= 16 partials in lanes 0..15)
             const int gx = (g.N + 31) >> 5, gy = (g.M + 31) >> 5;
@@ -562,9 +597,9 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                         t4[j] = pol ? *reinterpret_cast<const f4 *>(g.tw + a) : (f4){0.f, 0.f, 0.f, 0.f};
                     }
                 }
-                f4 sum = *reinterpret_cast<const f4 *>(lds + row * 64 + col);
+                f4 sum = *reinterpret_cast<const f4 *>(parked + row * 64 + col);
 #pragma unroll
-                for (int gq = 1; gq < KS; ++gq) sum += *reinterpret_cast<const f4 *>(lds + gq * (4 * TILE_FLOATS) + row * 64 + col);
+                for (int gq = 1; gq < KS; ++gq) sum += *reinterpret_cast<const f4 *>(parked + gq * (4 * TILE_FLOATS) + row * 64 + col);
                 g4[j] = sum;
             }
             GSTAMP(8);
@@ -588,11 +623,13 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
             if (FIXED || g.sumsq) {
                 ss = wave_sum(ss);
                 GSTAMP(10);
-                lds_barrier();  // red[] (bias partials) and the partial tiles have been consumed
-                GSTAMP(11);
-                if (lane == 0) red[tid_all >> 6] = ss;
-                lds_barrier();
-                GSTAMP(12);
+                if constexpr (!LEAN_HANDOFF) {
+                    lds_barrier();  // red[] (bias partials) and the partial tiles have been consumed
+                    GSTAMP(11);
+                    if (lane == 0) red[tid_all >> 6] = ss;
+                    lds_barrier();
+                    GSTAMP(12);
+                }
                 // (the sum of the wave partials and the slot stores: sumsq_finish, behind the optimizer stores)
             }
             GSTAMP(9);
@@ -628,6 +665,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                     if (pol && g.tb) g.tb[bi_] = btv_ * (1.0f - tau) + pn * tau;
                 }
             }
+            if constexpr (LEAN_HANDOFF) sumsq_handoff(ss);
             sumsq_finish();
             GSTAMP(4);
             return;
@@ -639,9 +677,9 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         for (int j = 0; j < PER; ++j) {
             const int idx = tid_all + j * NT_ALL;
             const int row = idx >> 6, col = idx & 63;
-            float sum = lds[idx];
+            float sum = parked[idx];
 #pragma unroll
-            for (int gq = 1; gq < KS; ++gq) sum += lds[gq * (4 * TILE_FLOATS) + idx];
+            for (int gq = 1; gq < KS; ++gq) sum += parked[gq * (4 * TILE_FLOATS) + idx];
             gval[j] = sum;
             ok[j] = (m0 + row) < g.M && (n0 + col) < g.N;
             ci[j] = coff + (int64_t)(m0 + row) * g.ldc + n0 + col;
@@ -673,9 +711,11 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         if (bias_thr) ss += bsum * bsum;
         if (FIXED || g.sumsq) {
             ss = wave_sum(ss);
-            __syncthreads();  // red[] (bias partials) has been consumed
-            if (lane == 0) red[tid_all >> 6] = ss;
-            __syncthreads();
+            if constexpr (!LEAN_HANDOFF) {
+                __syncthreads();  // red[] (bias partials) has been consumed
+                if (lane == 0) red[tid_all >> 6] = ss;
+                __syncthreads();
+            }
         }
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
@@ -703,6 +743,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                 if (pol && g.tb) g.tb[bi] = btv * (1.0f - tau) + pn * tau;
             }
         }
+        if constexpr (LEAN_HANDOFF) sumsq_handoff(ss);
         sumsq_finish();
         GSTAMP(4);
         return;
@@ -899,6 +940,7 @@ __global__ __launch_bounds__(NTHREADS *KS) void ens_gemm_pair_kernel(GemmPair p)
 constexpr int FX_H = 256;                       // hidden width
 constexpr int FX_GRID = FX_H / BM;              // 4: tile rows of both problems, tile columns of fc2, head workgroups per net
 constexpr int FX_TILES2 = FX_GRID * FX_GRID;    // fc2 tiles per net
+constexpr int FX_WSUM = 16;   // LDS floats behind red[]: a tile's 16 gradient-norm wave partials (ens_gemm_body: wsum)
 
 // The compact argument block: what the fixed form reads and nothing else.  An fc2 tile's words come first and together
 // (its two operands, the arena bases, the control block, the W3 snapshot: one 64-byte scalar load), the layer offsets are
@@ -965,7 +1007,7 @@ __global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArg
         bid = slot < a8 ? x * a8 + slot
                         : (slot < a8 + f8 ? p.tiles0 + x * f8 + (slot - a8) : p.tiles01 + x * h8 + (slot - a8 - f8));
     }
-    float *tab = lds + KS * (4 * TILE_FLOATS) + 64 * KS;  // folded loss gradient: [n_rows] row scales, then scratch
+    float *tab = lds + KS * (4 * TILE_FLOATS) + 64 * KS + FX_WSUM;  // folded loss gradient: [n_rows] row scales, then scratch
     const LateTau lt{p.late_word != nullptr, p.late_word ? *p.late_word : 0u};
     int last = 0;
     bool drawn = false;
@@ -1483,10 +1525,12 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
     const int total = p.tiles01 + p.head_total + p.td_wg;
     if constexpr (TN_ && EPI == EPI_ADAM && KS == 4) {
         // the fixed-shape form (wgrad_fixed_kernel): per launch, from what the launch itself says
-        if (lean && g_wgrad_fixed && wgrad_fixed_ok(p, batch0, total)) {
+        // (its LDS block is FX_WSUM floats longer; a launch whose loss table leaves no room for them keeps the general kernel)
+        const size_t lds_fixed = lds + sizeof(float) * FX_WSUM;
+        if (lean && g_wgrad_fixed && lds_fixed <= PAIR_LDS_MAX && wgrad_fixed_ok(p, batch0, total)) {
             static bool raised_fixed = false;
             if (ssac_raise_lds(raised_fixed, PAIR_LDS_MAX, "wgrad_fixed", wgrad_fixed_kernel)) return 1;
-            SSAC_LAUNCH(wgrad_fixed_kernel, dim3(total), dim3(NTHREADS * KS), lds, st, wgrad_fixed_args(p));
+            SSAC_LAUNCH(wgrad_fixed_kernel, dim3(total), dim3(NTHREADS * KS), lds_fixed, st, wgrad_fixed_args(p));
             g_wgrad_fixed_taken = 1;
             return ssac_check_launch("wgrad_fixed");
         }

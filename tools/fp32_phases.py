@@ -44,3 +44,9 @@ print("wgrad tile 0 prologue (serialised by the debug stamps): first operand chu
       " LDS stores + second chunk", g[7] - g[6], " barrier + first fragment reads", g[1] - g[7])
 print("wgrad tile 0 epilogue: partial sums from LDS", g[8] - g[3], " gradient-norm partial (2 barriers)", g[9] - g[8], " Adam + stores issued", g[4] - g[9])
 print("   gradient-norm partial: squares + wave sum", g[10] - g[8], " first barrier", g[11] - g[10], " second barrier", g[12] - g[11], " sum of 16 + slot stores", g[9] - g[12])
+# (stamp 14: thread 0's wave has issued its partials' LDS stores -- the hand-off splits into skew / stores / barrier.  The fixed
+# form takes the norm's hand-off behind the optimizer stores: there stamps 9 / 11 / 12 / 4 read Adam start / stores issued /
+# the norm's barrier released / end, and the line above does not apply)
+print("wgrad tile 0 hand-off: last MFMA -> partials' stores issued", g[14] - g[2], " -> barrier released", g[3] - g[14])
+print("wgrad tile 0, norm behind the stores (fixed form): Adam + stores issued", g[11] - g[9], " norm's write + barrier", g[12] - g[11],
+      " end (thread 0 takes no part in the sum)", g[4] - g[12])
