@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 10
+#define SSAC_ABI_VERSION 11
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -1023,6 +1023,31 @@ int ssac_ln_tanh_fwd(const float *x, int64_t ldx, const float *gamma, const floa
 int ssac_ln_tanh_bwd(const float *d_out, int64_t ldd, const float *out, int64_t ldo, const float *xhat,
                      const float *rstd, const float *gamma, int n_rows, int dim, float *dx, int64_t ldx,
                      float *dy_scratch, float *dgamma, float *dbeta, void *stream);
+
+/* ==== two-layer MLP encoders (csrc/ssac_enc_mlp.hip): obs -> Linear(K, H) -> ReLU -> Linear(H, N) -> act2, the reference's
+ * SharedEncoder (experiments/gym/train_gym.py) and VisgridEncoder (experiments/visgrid/train.py).  W0 (H x K), W1 (N x H)
+ * row-major and tight, as nn.Linear stores them.  act / act2: 0 = none, 1 = ReLU, 2 = tanh.  Exact fp32 (MFMA f32), no
+ * atomics: a replay is bit-identical.
+ * Per layer the encoder runs on ssac_linear_fwd / ssac_linear_dgrad_masked / ssac_linear_wgrad_splitk plus the two
+ * elementwise passes below: Y <- act(Y) in place on an (M x N, ldy) block, and dZ (M x N, tight) = act'(Y) * dY with the
+ * derivative taken from the activation's OUTPUT (ReLU: [y > 0], tanh: 1 - y^2). */
+int ssac_enc_act_fwd(float *Y, int64_t ldy, int M, int N, int act, void *stream);
+int ssac_enc_act_bwd(const float *dY, int64_t ldd, const float *Y, int64_t ldy, int M, int N, int act, float *dZ,
+                     void *stream);
+/* Both layers in ONE launch, a workgroup per 32 rows, the hidden tile kept in LDS.
+ * Covered (ssac_enc_mlp2_covered): H % 32 == 0, 32 <= H <= 256; 1 <= K, N <= 2^20; 1 <= M <= 2^24; any ldx >= K,
+ * ldy >= N; W1 16-byte aligned.  Row, K and N tails are guarded.  ssac_enc_mlp2_supported: covered AND the fused forward
+ * measured faster than the per-layer launches (profiles/mlp_encoder.md: K <= 32); the launches themselves accept every
+ * covered shape.
+ *   fwd: h = relu(X W0^T + b0) -> H_save (M x H, tight) when not NULL; Y[:, :N] = act2(h W1^T + b1)
+ *   bwd: dZ1 (M x N, tight) = act2'(Y) * dY; dZ0 (M x H, tight) = [H_save > 0] * (dZ1 W1) -- the operands of the two
+ *        weight-gradient products (ssac_linear_wgrad_splitk); no dX: observations need no gradient */
+int ssac_enc_mlp2_covered(int M, int K, int H, int N);
+int ssac_enc_mlp2_supported(int M, int K, int H, int N);
+int ssac_enc_mlp2_fwd(const float *X, int64_t ldx, const float *W0, const float *b0, const float *W1, const float *b1,
+                      int M, int K, int H, int N, int act2, float *H_save, float *Y, int64_t ldy, void *stream);
+int ssac_enc_mlp2_bwd(const float *dY, int64_t ldd, const float *Y, int64_t ldy, const float *H_save, const float *W1,
+                      int M, int H, int N, int act2, float *dZ1, float *dZ0, void *stream);
 
 /* ==== bf16-operand mode (csrc/ssac_bf16.hip): BASELINE.json config 2.  No reference counterpart (the reference is
  * fp32 only, super_sac/__init__.py:3): fp32 master weights / Adam moments / Polyak targets as above, matrix products

@@ -31,6 +31,7 @@ from . import learning  # noqa: E402,F401
 from . import adv_estimator  # noqa: E402,F401
 from . import checkpoint  # noqa: E402,F401
 from . import conv_encoder  # noqa: E402,F401
+from . import mlp_encoder  # noqa: E402,F401
 from . import parallel  # noqa: E402,F401
 from . import adopt  # noqa: E402,F401
 from .adopt import adopt_agent, adopt_augmenter, adopt_buffer  # noqa: E402,F401

@@ -215,6 +215,12 @@ SIGNATURES = {
     "ssac_sumsq": [_P, _L, _P, _P],
     "ssac_ln_tanh_fwd": [_P, _L, _P, _P, _I, _I, _P, _L, _P, _P, _P],
     "ssac_ln_tanh_bwd": [_P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P],
+    "ssac_enc_act_fwd": [_P, _L, _I, _I, _I, _P],
+    "ssac_enc_act_bwd": [_P, _L, _P, _L, _I, _I, _I, _P, _P],
+    "ssac_enc_mlp2_covered": [_I, _I, _I, _I],
+    "ssac_enc_mlp2_supported": [_I, _I, _I, _I],
+    "ssac_enc_mlp2_fwd": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P],
+    "ssac_enc_mlp2_bwd": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "ssac_fused_supported": [_MP],
     "ssac_fused_row_tiles": [_MP, _I, _I],
     "ssac_step_polyak": [_P, _F],
@@ -302,7 +308,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def _load():

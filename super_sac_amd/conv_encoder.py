@@ -84,6 +84,7 @@ class ConvEncoderEngine:
                 v.copy_(p.data.to(device=device, dtype=torch.float32))
                 p.data = v
         self.grads = torch.zeros_like(self.flat)
+        self.moments_key = "conv_encoder"   # of this arena's Adam moments in the optimizer's group
         self.ws = engine.Workspace(device)
         self.saved = None
 
@@ -342,7 +343,7 @@ class ConvEncoderEngine:
             check(lib.ssac_group_norms(ss.data_ptr(), 1, nb, adam.ctl.ptr, norm_out.data_ptr(), st))
         if not step:
             return
-        m, v = adam.moments_for("conv_encoder", self.flat)
+        m, v = adam.moments_for(self.moments_key, self.flat)
         check(lib.ssac_adam_step(self.flat.data_ptr(), m.data_ptr(), v.data_ptr(), self.grads.data_ptr(),
                                  self.numel, adam.ctl.ptr, st))
 

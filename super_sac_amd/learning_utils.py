@@ -482,15 +482,16 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
 # ------------------------------------------------------------------------------------------
 def encode(encoder, obs_dict, dst=None, save=False):
     """state representation of the batch: identity encoders return the (strided) view; pixel
-    encoders run the HIP conv engine (conv_encoder.py) and write into `dst[:, :emb]` when given."""
+    encoders run the HIP conv engine (conv_encoder.py), two-layer MLP encoders theirs (mlp_encoder.py), and write
+    into `dst[:, :emb]` when given."""
     key = getattr(encoder, "ssac_identity_key", None)
     if key is not None:
         return obs_dict[key]
-    from . import conv_encoder
-    img = obs_dict[getattr(encoder, "ssac_obs_key", "obs")]
-    eng = conv_encoder.conv_engine(encoder, img.device)
+    from . import mlp_encoder
+    eng = mlp_encoder.encoder_engine(encoder, next(iter(obs_dict.values())).device, obs_dict)
     if eng is None:
         raise NotImplementedError(f"{type(encoder).__name__}: this encoder has no HIP path")
+    img = obs_dict[getattr(encoder, "ssac_obs_key", "obs")]
     if dst is None:
         dst = torch.empty(img.shape[0], eng.emb, device=img.device)
     eng.forward(img, dst, dst.stride(0), save)
@@ -513,7 +514,10 @@ def ensure_adopted(agent, buffer=None):
         adopt.adopt_buffer(buffer, next(agent.actors[0].parameters()).device)
     st = getattr(buffer, "_storage", None) if buffer is not None else None
     if st is not None and not is_identity(agent.encoder):
-        adopt.probe_identity(agent.encoder, {k: v[:1].float() for k, v in st.s_stack.items()})
+        rows = {k: v[:1].float() for k, v in st.s_stack.items()}
+        if adopt.probe_identity(agent.encoder, rows) is None:
+            from . import mlp_encoder
+            mlp_encoder.find_mlp_encoder(agent.encoder, rows)   # (two-layer MLP encoders: recognised once, here)
 
 
 def _row_stride(t):

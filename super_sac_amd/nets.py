@@ -167,6 +167,37 @@ class IdentityEncoder(Encoder):
         return obs_dict[self.ssac_identity_key]
 
 
+class MlpEncoder(Encoder):
+    """A trainable two-layer encoder of one vector (or flattened) observation: flatten -> fc1 -> ReLU -> fc2 -> out_act.
+    ``MlpEncoder(dim, 128, dim)`` is the function of the reference's ``--shared_encoder``, ``MlpEncoder((18, 18), 256, 2,
+    out_act="tanh")`` that of its visgrid encoder.  A parameter container like the other modules here: the arithmetic
+    runs on mlp_encoder.MlpEncoderEngine."""
+
+    def __init__(self, in_shape, hidden, out_dim, out_act="relu", key="obs"):
+        super().__init__()
+        assert out_act in ("relu", "tanh", "none"), f"unknown out_act {out_act!r}"
+        shape = (int(in_shape),) if isinstance(in_shape, int) else tuple(int(s) for s in in_shape)
+        self.fc1 = nn.Linear(int(math.prod(shape)), hidden)
+        self.fc2 = nn.Linear(hidden, out_dim)
+        for m in (self.fc1, self.fc2):
+            weight_init(m)
+        self.ssac_obs_key, self.ssac_obs_shape, self.ssac_mlp_act = key, shape, out_act
+        self._dim = out_dim
+
+    @property
+    def embedding_dim(self):
+        return self._dim
+
+    def forward(self, obs_dict):
+        from . import mlp_encoder
+        x = obs_dict[self.ssac_obs_key]
+        engine.require_gpu(x)
+        eng = mlp_encoder.mlp_engine(self, x.device)
+        out = torch.empty(x.shape[0], self._dim, device=x.device)
+        eng.forward(x.float(), out, self._dim, save=False)
+        return out
+
+
 class _PixelEncoderBase(nn.Module):
     """parameter container of a convolutional encoder; arithmetic lives in conv_encoder.py"""
 
