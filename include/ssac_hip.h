@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 11
+#define SSAC_ABI_VERSION 12
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -1049,7 +1049,34 @@ int ssac_enc_mlp2_fwd(const float *X, int64_t ldx, const float *W0, const float 
 int ssac_enc_mlp2_bwd(const float *dY, int64_t ldd, const float *Y, int64_t ldy, const float *H_save, const float *W1,
                       int M, int H, int N, int act2, float *dZ1, float *dZ0, void *stream);
 
-/* ==== bf16-operand mode (csrc/ssac_bf16.hip): BASELINE.json config 2.  No reference counterpart (the reference is
+/* ==== plain two-layer convolution stacks on small maps (csrc/ssac_enc_convstack.hip): the reference's MinAtar encoder
+ * (experiments/minatar/minatar_utils.py:37-63) ahead of its fc:
+ *   h1 = relu(conv k1 (C -> co1)(x / div + shift)),  h2 = relu(conv k2 (co1 -> co2)(h1)),  flat = h2 in NCHW order
+ * X (B x C x H x W, tight) is fp32, or uint8 with u8 = 1 (cast and normalised in the staging loads; div 1, shift 0 leaves
+ * the values as they are); W1 (co1 x C x k1 x k1), W2 (co2 x co1 x k2 x k2) as nn.Conv2d stores them.  Exact fp32
+ * (v_mfma_f32_16x16x4_f32), no atomics: a replay is bit-identical.  A workgroup owns SSAC_ENC_CONVSTACK_TILE images.
+ * Covered (ssac_enc_convstack_covered): co1 == co2 == 16, s1 == s2 == 1, 1 <= C <= 16, 1 <= k1, k2 <= 4,
+ * k1 + k2 - 1 <= H, W <= 32, and a tile's working set (images, first map, masked gradient, weights, index tables) within
+ * the 64 KiB of LDS a launch asks for -- e.g. 10 x 10 frames with C <= 16, 12 x 12 frames with C <= 4, no 16 x 16 frames.  1 <= B <= 2^22.
+ * ssac_enc_convstack_supported: covered AND the fused form measured faster than the per-layer launches
+ * (profiles/conv_stack_encoder.md); the launches themselves accept every covered geometry, and any other call returns an
+ * error status before anything is launched.
+ *   fwd: h1 -> H1_save (B x co1 x P1, tight) when not NULL; out (B x co2 P2, tight) = flat, the input of the fc
+ *        (ssac_linear_fwd with the fc weight as it is stored: no permutation)
+ *   bwd: d_flat (B x co2 P2, tight) = dL/d(flat) from the fc's backward-data launch; H1, H2 = what fwd wrote.  partial
+ *        ((B + TILE - 1) / TILE slices x 16 (C k1 k1 + 16 k2 k2 + 2)): per workgroup [dW1 | db1 | dW2 | db2], the layout of a
+ *        parameter arena that holds the four tensors back to back; sum with ssac_reduce_slices (fixed order).  No dX. */
+#define SSAC_ENC_CONVSTACK_TILE 4
+int ssac_enc_convstack_covered(int C, int H, int W, int co1, int k1, int s1, int co2, int k2, int s2);
+int ssac_enc_convstack_supported(int B, int C, int H, int W, int co1, int k1, int s1, int co2, int k2, int s2);
+int ssac_enc_convstack_fwd(const void *X, int u8, const float *W1, const float *b1, const float *W2, const float *b2, int B,
+                           int C, int H, int W, int co1, int k1, int s1, int co2, int k2, int s2, float div, float shift,
+                           float *H1_save, float *out, void *stream);
+int ssac_enc_convstack_bwd(const float *d_flat, const void *X, int u8, const float *H1, const float *H2, const float *W2,
+                           int B, int C, int H, int W, int co1, int k1, int s1, int co2, int k2, int s2, float div,
+                           float shift, float *partial, void *stream);
+
+/* ==== bf16-operand mode (csrc/ssac_bf16.hip): BASELINE.json config 2. No reference counterpart (the reference is
  * fp32 only, super_sac/__init__.py:3): fp32 master weights / Adam moments / Polyak targets as above, matrix products
  * on v_mfma_f32_32x32x16_bf16 (bf16 operands, fp32 accumulate) fed from a bf16 SHADOW arena per net
  *   [ W1 (hidden x K1P, K zero-padded to 16) | W2 | W2^T | W3 ]        (ssac_bf16_layout: stride + the 4 offsets)

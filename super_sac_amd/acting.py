@@ -116,10 +116,10 @@ def _conv_module(agent):
 def _pixel_obs(agent, obs, num_envs):
     """(key, (C, H, W), dtype) when the observation is a uint8 -- with FLOAT32_FRAMES also a float32 -- image batch for a pixel
     encoder of this package, else None (float64 and every other dtype: the general path)"""
+    conv = _conv_module(agent)   # (first: recognising a plain conv stack settles its observation key)
     key = getattr(agent.encoder, "ssac_obs_key", None)
     if key is None:
         return None
-    conv = _conv_module(agent)
     v = obs.get(key)
     if conv is None or not isinstance(v, np.ndarray) or not (v.dtype == np.uint8 or (FLOAT32_FRAMES and v.dtype == np.float32)):
         return None

@@ -13,9 +13,12 @@ with channels-last activations, so each GEMM output is the next layer's input an
 fixed order), leaving the gradients in one flat arena so clip_grad_norm_ and Adam are two launches.
 The module's parameters are re-pointed at a flat arena exactly like the MLP ensembles.
 """
+import copy
 import ctypes as C
+import math
 
 import torch
+from torch import nn
 
 from . import engine
 from ._lib import check, lib
@@ -36,15 +39,130 @@ WGRAD_WHOLE_IMAGES = True        # weight gradients of layers with small feature
 FC_STREAM = True  # the fc forward as an operand stream (N <= 64 outputs; DMC 49 -> 38 us per pass)
 FC_SLICES = 48  # K slices of the tiled fc forward (8 row tiles x 48 slices ~ 1.5 workgroups per CU at B 512)
 ROWS_PER_SLICE = 4096  # split-K granularity of the convolution weight gradients
+# plain two-layer conv stacks (MinAtar): True: ssac_enc_convstack_fwd / _bwd where ssac_enc_convstack_supported says they
+# measured faster than the per-layer launches (profiles/conv_stack_encoder.md); False: every layer on its own launches;
+# "all": the fused launches wherever the geometry is covered (the tests' switch)
+STACK_FUSED = True
+STACK_BWD_MIN_ROWS = 32   # batch from which a pass that keeps its activations (a backward follows) takes the fused form: the
+                          # fused backward measured faster at B 32 .. 1024 and slower at B 1 (54 against 41 us at C 16)
+STACK_TILE = 4   # images per workgroup of the fused launches (SSAC_ENC_CONVSTACK_TILE): one weight-gradient partial each
+
+_KNOWN_PIXEL = ("BigPixelEncoder", "SmallPixelEncoder")   # cnns.py:37-103: their input normalisation is known, not probed
+_STACK_INPUTS = ((1.0, 0.0), (255.0, 0.0))                # (div, shift) candidates of a plain conv stack: raw, x / 255
+_PROBE_ROWS = 4
+_PROBE_TOL = 1e-5
+
+
+def _stack_layers(m):
+    """(convs, fc) when `m` has the STRUCTURE of a plain conv stack: conv1..convN (N <= 4, no gap) of square, unpadded,
+    undilated, ungrouped fp32 nn.Conv2d that chain, an nn.Linear fc, no ln; else None"""
+    names = [n for n in ("conv1", "conv2", "conv3", "conv4") if hasattr(m, n)]
+    if not names or names != ["conv1", "conv2", "conv3", "conv4"][:len(names)] or hasattr(m, "conv5") or hasattr(m, "ln"):
+        return None
+    convs, fc = [getattr(m, n) for n in names], getattr(m, "fc", None)
+    if not isinstance(fc, nn.Linear) or fc.bias is None or fc.weight.dtype != torch.float32:
+        return None
+    for c in convs:
+        if not isinstance(c, nn.Conv2d) or c.bias is None or c.weight.dtype != torch.float32:
+            return None
+        if c.kernel_size[0] != c.kernel_size[1] or c.stride[0] != c.stride[1] or c.groups != 1:
+            return None
+        if tuple(c.dilation) != (1, 1) or c.padding not in ((0, 0), "valid", 0):
+            return None
+    if any(a.out_channels != b.in_channels for a, b in zip(convs, convs[1:])):
+        return None
+    return convs, fc
+
+
+def _probe_shape(m, convs, fc):
+    """an input (C, H, W) the stack accepts: the module's own ``ssac_obs_shape``, else the one nearest to a square whose
+    last map fills fc.in_features (the frame's true shape is not needed: any accepted size shows what the module computes)"""
+    shape = getattr(m, "ssac_obs_shape", None)
+    if shape is not None and len(shape) == 3:
+        return tuple(int(v) for v in shape)
+    pixels, rest = divmod(fc.in_features, convs[-1].out_channels)
+    if rest or pixels < 1:
+        return None
+    h = next(s for s in range(math.isqrt(pixels), 0, -1) if pixels % s == 0)
+    w = pixels // h
+    for c in reversed(convs):
+        h, w = (h - 1) * c.stride[0] + c.kernel_size[0], (w - 1) * c.stride[0] + c.kernel_size[0]
+    return convs[0].in_channels, h, w
+
+
+def stack_function(x, convs, fc, div, shift):
+    """fc(flatten_NCHW(relu(convN(... relu(conv1(x / div + shift)))))): what a plain conv stack computes"""
+    h = x if div == 1.0 and shift == 0.0 else x / div + shift
+    for c in convs:
+        h = torch.relu(nn.functional.conv2d(h, c.weight, c.bias, stride=c.stride))
+    return nn.functional.linear(h.flatten(1), fc.weight, fc.bias)
+
+
+def _probe_stack(encoder, m):
+    """(div, shift) of the plain conv stack `m` inside `encoder`, or False.  The module's OWN forward is evaluated on a few
+    random frames and compared with stack_function for every candidate -- on a CPU copy (no torch convolution runs on the
+    GPU on this engine's account) and with a local generator (no global random stream moves)."""
+    layers = _stack_layers(m)
+    if layers is None:
+        return False
+    shape = _probe_shape(m, *layers)
+    if shape is None:
+        return False
+    name = next(n for n, sub in encoder.named_modules() if sub is m)
+    try:
+        cpu = copy.deepcopy(encoder).to("cpu")
+    except Exception:
+        return False
+    cpu_m = cpu.get_submodule(name) if name else cpu
+    convs, fc = _stack_layers(cpu_m)
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(0x5eed)
+    x = torch.randint(0, 256, (_PROBE_ROWS,) + shape, generator=gen).to(torch.float32)
+    key = getattr(encoder, "ssac_obs_key", "obs")
+    with torch.no_grad():
+        try:
+            out = cpu({key: x})
+        except Exception:
+            try:
+                out = cpu_m(x)
+            except Exception:
+                return False
+        if not torch.is_tensor(out) or tuple(out.shape) != (_PROBE_ROWS, fc.out_features):
+            return False
+        for div, shift in _STACK_INPUTS:
+            if bool(((out.float() - stack_function(x, convs, fc, div, shift)).abs() <= _PROBE_TOL).all()):
+                encoder.__dict__.setdefault("ssac_obs_key", key)
+                return div, shift
+    return False
 
 
 def find_conv_module(encoder):
-    """the BigPixelEncoder/SmallPixelEncoder-shaped module inside an Encoder wrapper
-    (train_dmc_from_pixels.py:15-27 ``conv_block``, train_atari.py:9-20 ``cnn``)."""
+    """the convolutional module inside an Encoder wrapper: a BigPixelEncoder / SmallPixelEncoder-shaped one
+    (train_dmc_from_pixels.py:15-27 ``conv_block``, train_atari.py:9-20 ``cnn``: by class name, or by its ``ln``), or a
+    plain conv stack (experiments/minatar/minatar_utils.py:37-63), whose input normalisation is declared
+    (nets.ConvStackEncoder) or found by a one-off probe and cached on the module.  A module with ``conv1`` and ``fc`` that
+    is neither raises: it has no HIP path."""
     for m in encoder.modules():
         if hasattr(m, "conv1") and hasattr(m, "fc"):
+            if hasattr(m, "ln") or any(k.__name__ in _KNOWN_PIXEL for k in type(m).__mro__):
+                return m
+            if getattr(m, "ssac_conv_input", None) is not None:
+                return m
+            found = m.__dict__.get("_ssac_conv_input")
+            if found is None:
+                found = m.__dict__["_ssac_conv_input"] = _probe_stack(encoder, m)
+            if not found:
+                raise NotImplementedError(f"{type(encoder).__name__}: this encoder has no HIP path")
             return m
     return None
+
+
+def conv_input(module):
+    """(div, shift) of the first layer's input normalisation x / div + shift"""
+    if hasattr(module, "ln"):
+        return 255.0, -0.5
+    found = getattr(module, "ssac_conv_input", None) or module.__dict__.get("_ssac_conv_input")
+    return (float(found[0]), float(found[1])) if found else (255.0, 0.0)
 
 
 class ConvEncoderEngine:
@@ -63,7 +181,7 @@ class ConvEncoderEngine:
                             for l, (ci, co, k, s) in enumerate(self.geom)]
         self.implicit = list(self.implicit_ok)
         self.first = False   # the saved forward ran the first layer as an implicit GEMM
-        self.div, self.shift = (255.0, -0.5) if self.big else (255.0, 0.0)
+        self.div, self.shift = conv_input(module)
         # ---- flat parameter arena (each tensor starts at a multiple of 4 floats)
         plist = []
         for c in convs:
@@ -91,6 +209,18 @@ class ConvEncoderEngine:
     def is_bound(self):
         return all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(self.plist, self.offs))
 
+    def stack_fused(self, B, H, W, save=False):
+        """a B-image batch of H x W frames takes the fused launches of a plain two-layer stack (`save`: forward AND the
+        backward that follows it, which is tied to the forward's form)"""
+        if not STACK_FUSED or self.big or len(self.geom) != 2:
+            return False
+        (c, co1, k1, s1), (_, co2, k2, s2) = self.geom
+        if STACK_FUSED == "all":
+            return bool(lib.ssac_enc_convstack_covered(c, H, W, co1, k1, s1, co2, k2, s2))
+        if save and B < STACK_BWD_MIN_ROWS:
+            return False
+        return bool(lib.ssac_enc_convstack_supported(B, c, H, W, co1, k1, s1, co2, k2, s2))
+
     def _seg(self, k, tensor=None):
         t = self.flat if tensor is None else tensor
         return t[self.offs[k]:self.offs[k] + self.plist[k].numel()]
@@ -115,7 +245,20 @@ class ConvEncoderEngine:
         Hi, Wi, div, shift = Hh, Ww, self.div, self.shift
         cols, ys, shapes = [], [], []
         tag = "s" if save else "t"
-        for l, (ci, co, k, s) in enumerate(self.geom):
+        fused = self.stack_fused(B, Hh, Ww, save)
+        if fused:
+            # both convolutions in one launch (csrc/ssac_enc_convstack.hip): the first map goes to memory only for backward,
+            # the second is written in NCHW flatten order -- the fc's input as its weight is stored
+            (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
+            Hi, Wi = Hh - k1 + 1 - k2 + 1, Ww - k1 + 1 - k2 + 1
+            h1 = self.ws.get("s.h1", (B * co1 * (Hh - k1 + 1) * (Ww - k1 + 1),)) if save else None
+            src = self.ws.get(f"{tag}.flat", (B * co2 * Hi * Wi,))
+            check(lib.ssac_enc_convstack_fwd(img_ptr, u8, self.convs[0].weight.data_ptr(), self.convs[0].bias.data_ptr(),
+                                             self.convs[1].weight.data_ptr(), self.convs[1].bias.data_ptr(), B, Cc, Hh, Ww,
+                                             co1, k1, s1, co2, k2, s2, div, shift, h1.data_ptr() if save else 0,
+                                             src.data_ptr(), st))
+            ys = [h1, src]
+        for l, (ci, co, k, s) in (() if fused else enumerate(self.geom)):   # (per layer: no pass once the stack ran fused)
             Ho, Wo = (Hi - k) // s + 1, (Wi - k) // s + 1
             rows, ckk = B * Ho * Wo, ci * k * k
             y = self.ws.get(f"{tag}.y{l if save else l % 2}", (rows * co,))
@@ -149,7 +292,9 @@ class ConvEncoderEngine:
         co = self.geom[-1][1]
         flat_dim = co * Hi * Wi
         fc = self.module.fc
-        if FC_CHANNELS_LAST:
+        if fused:
+            colf, wfc = src, fc.weight
+        elif FC_CHANNELS_LAST:
             # the last feature map IS the fc input once the weight's columns are put in channels-last order
             # (emb x C x P -> emb x P x C, 7.8 MB for DrQ: cheaper than gathering B x C*P activations both ways)
             colf = src
@@ -199,7 +344,7 @@ class ConvEncoderEngine:
             xhat = rstd = None
             fc_forward(dst_ptr, ld_dst)
         if save:
-            self.saved = dict(B=B, img=img, cols=cols, ys=ys, shapes=shapes, colf=colf, wfc=wfc, flat_dim=flat_dim,
+            self.saved = dict(B=B, img=img, img_ptr=img_ptr, u8=u8, shape=(Cc, Hh, Ww), fused=fused, cols=cols, ys=ys, shapes=shapes, colf=colf, wfc=wfc, flat_dim=flat_dim,
                               Hf=Hi, Wf=Wi, xhat=xhat, rstd=rstd, out=dst, ld_out=ld_dst)
 
     # ------------------------------------------------------------------------------------
@@ -234,6 +379,25 @@ class ConvEncoderEngine:
         else:
             dz = d_rep
         flat_dim = sv["flat_dim"]
+        if sv["fused"]:
+            # fc on the NCHW flatten as it is stored: weight gradient straight into the arena, backward-data, then both
+            # layers' gradients as one partial per image tile, summed in a fixed order into the arena's first four tensors
+            (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
+            Cc, Hh, Ww = sv["shape"]
+            check(lib.ssac_linear_wgrad_splitk(dz.data_ptr(), self.emb, sv["colf"].data_ptr(), flat_dim,
+                                               self._seg(k_fcw, self.grads).data_ptr(),
+                                               self._seg(k_fcb, self.grads).data_ptr(), self.emb, flat_dim, B, B, st))
+            dflat = self.ws.get("b.dflat", (B * flat_dim,))
+            check(lib.ssac_linear_dgrad(dz.data_ptr(), self.emb, self.module.fc.weight.data_ptr(), flat_dim,
+                                        dflat.data_ptr(), flat_dim, B, flat_dim, self.emb, st))
+            slices, n = (B + STACK_TILE - 1) // STACK_TILE, self.offs[4]
+            assert n == co1 * (ci * k1 * k1 + 1) + co2 * (co1 * k2 * k2 + 1)   # (the four tensors lie back to back)
+            part = self.ws.get("b.pstack", (slices * n,))
+            check(lib.ssac_enc_convstack_bwd(dflat.data_ptr(), sv["img_ptr"], sv["u8"], sv["ys"][0].data_ptr(),
+                                             sv["ys"][1].data_ptr(), self.convs[1].weight.data_ptr(), B, Cc, Hh, Ww, co1, k1,
+                                             s1, co2, k2, s2, self.div, self.shift, part.data_ptr(), st))
+            check(lib.ssac_reduce_slices(part.data_ptr(), slices, n, self.grads.data_ptr(), st))
+            return
         ci, co, k, s, Hi, Wi, Ho, Wo = sv["shapes"][-1]
         dy = self.ws.get(f"b.dy{(nconv - 1) % 2}", (B * Ho * Wo * co,))
         ylast = sv["ys"][-1]

@@ -251,6 +251,41 @@ class SmallPixelEncoder(_PixelEncoderBase):
         self.embedding_dim = out_dim
 
 
+class ConvStackEncoder(Encoder):
+    """A plain convolution stack on one image observation: conv1..convN (square kernels, no padding) each followed by
+    ReLU, NCHW flatten, fc; input x / input_div, no LayerNorm, no output activation.  The defaults are the function of the
+    reference's MinAtar encoder (experiments/minatar/minatar_utils.py:37-63: conv3x3 (C -> 16), conv2x2 (16 -> 16),
+    fc -> 50 on raw 10 x 10 frames).  A parameter container like the other modules here: the arithmetic runs on
+    conv_encoder.ConvEncoderEngine."""
+
+    def __init__(self, obs_shape, convs=((16, 3, 1), (16, 2, 1)), out_dim=50, input_div=1.0, key="obs"):
+        super().__init__()
+        assert 1 <= len(convs) <= 4, "ConvStackEncoder: one to four conv layers"
+        c, h, w = (int(v) for v in obs_shape)
+        self.ssac_obs_key, self.ssac_obs_shape = key, (c, h, w)
+        self.ssac_conv_input = (float(input_div), 0.0)
+        for i, (co, k, s) in enumerate(convs):
+            setattr(self, f"conv{i + 1}", nn.Conv2d(c, co, kernel_size=k, stride=s))
+            c, h, w = co, _conv_out(h, k, s), _conv_out(w, k, s)
+        assert h >= 1 and w >= 1, "ConvStackEncoder: the kernels do not fit the frame"
+        self.fc = nn.Linear(c * h * w, out_dim)
+        self.apply(weight_init)
+        self._dim = out_dim
+
+    @property
+    def embedding_dim(self):
+        return self._dim
+
+    def forward(self, obs_dict):
+        from . import conv_encoder
+        x = obs_dict[self.ssac_obs_key]
+        engine.require_gpu(x)
+        eng = conv_encoder.conv_engine(self, x.device)
+        out = torch.empty(x.shape[0], self._dim, device=x.device)
+        eng.forward(x if x.dtype == torch.uint8 else x.float(), out, self._dim, save=False)
+        return out
+
+
 class PixelEncoder(Encoder):
     """Encoder wrapper in the shape of the reference scripts' DMCPixelEncoder / AtariEncoder
     (train_dmc_from_pixels.py:15-27, train_atari.py:9-20): obs_dict["obs"] -> conv block."""
