@@ -10,11 +10,10 @@
 with channels-last activations, so each GEMM output is the next layer's input and the
 ``nn.Conv2d`` weights are used in place as (out, c*kh*kw) matrices.  The backward pass mirrors it
 (GEMM backward-data -> col2im with the ReLU mask fused; split-K weight-gradient GEMMs reduced in a
-fixed order), leaving the gradients in one flat arena so clip_grad_norm_ and Adam are two launches.
-The module's parameters are re-pointed at a flat arena exactly like the MLP ensembles.
+fixed order).  The parameter arena, the accumulate form of backward and the clip + Adam tail are
+``encoder_base.EncoderEngine``'s.
 """
 import copy
-import ctypes as C
 import math
 
 import torch
@@ -22,6 +21,7 @@ from torch import nn
 
 from . import engine
 from ._lib import check, lib
+from .encoder_base import EncoderEngine, cached_engine
 
 USE_IMPLICIT = True          # implicit-GEMM inner conv layers (False: every layer as im2col + GEMM; the tests' A/B)
 USE_IMPLICIT_FIRST = True    # the first layer as an implicit GEMM over the NCHW image
@@ -165,10 +165,11 @@ def conv_input(module):
     return (float(found[0]), float(found[1])) if found else (255.0, 0.0)
 
 
-class ConvEncoderEngine:
+class ConvEncoderEngine(EncoderEngine):
+    moments_key = "conv_encoder"
+
     def __init__(self, module, device):
         self.module = module
-        self.device = device
         convs = [getattr(module, n) for n in ("conv1", "conv2", "conv3", "conv4") if hasattr(module, n)]
         self.convs = convs
         self.big = hasattr(module, "ln")
@@ -182,32 +183,8 @@ class ConvEncoderEngine:
         self.implicit = list(self.implicit_ok)
         self.first = False   # the saved forward ran the first layer as an implicit GEMM
         self.div, self.shift = conv_input(module)
-        # ---- flat parameter arena (each tensor starts at a multiple of 4 floats)
-        plist = []
-        for c in convs:
-            plist += [c.weight, c.bias]
-        plist += [module.fc.weight, module.fc.bias]
-        if self.big:
-            plist += [module.ln.weight, module.ln.bias]
-        self.plist = plist
-        offs, o = [], 0
-        for p in plist:
-            offs.append(o)
-            o += (p.numel() + 3) // 4 * 4
-        self.offs, self.numel = offs, o
-        self.flat = torch.zeros(o, dtype=torch.float32, device=device)
-        with torch.no_grad():
-            for p, off in zip(plist, offs):
-                v = self.flat[off:off + p.numel()].view(p.shape)
-                v.copy_(p.data.to(device=device, dtype=torch.float32))
-                p.data = v
-        self.grads = torch.zeros_like(self.flat)
-        self.moments_key = "conv_encoder"   # of this arena's Adam moments in the optimizer's group
-        self.ws = engine.Workspace(device)
-        self.saved = None
-
-    def is_bound(self):
-        return all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(self.plist, self.offs))
+        layers = convs + [module.fc] + ([module.ln] if self.big else [])
+        self._pack([p for m in layers for p in (m.weight, m.bias)], device)
 
     def stack_fused(self, B, H, W, save=False):
         """a B-image batch of H x W frames takes the fused launches of a plain two-layer stack (`save`: forward AND the
@@ -220,10 +197,6 @@ class ConvEncoderEngine:
         if save and B < STACK_BWD_MIN_ROWS:
             return False
         return bool(lib.ssac_enc_convstack_supported(B, c, H, W, co1, k1, s1, co2, k2, s2))
-
-    def _seg(self, k, tensor=None):
-        t = self.flat if tensor is None else tensor
-        return t[self.offs[k]:self.offs[k] + self.plist[k].numel()]
 
     # ------------------------------------------------------------------------------------
     def forward(self, img, dst, ld_dst, save):
@@ -240,25 +213,64 @@ class ConvEncoderEngine:
         not a torch allocation.  Every launch reads / writes workspace buffers keyed by shape: recordable."""
         B, Cc, Hh, Ww = shape
         st = engine.stream()
+        tag = "s" if save else "t"
+        fused = self.stack_fused(B, Hh, Ww, save)
+        cols, ys, shapes, src, Hf, Wf = (self._forward_stack if fused else self._forward_layers)(img_ptr, shape, u8, tag, save)
+        co = self.geom[-1][1]
+        flat_dim = co * Hf * Wf
+        fc = self.module.fc
+        if fused:
+            colf, wfc = src, fc.weight
+        elif FC_CHANNELS_LAST:
+            # the last feature map IS the fc input once the weight's columns are put in channels-last order
+            # (emb x C x P -> emb x P x C, 7.8 MB for DrQ: cheaper than gathering B x C*P activations both ways)
+            colf = src
+            wfc = self.ws.get("fc.wcl", (self.emb * flat_dim,))
+            check(lib.ssac_permute_cp(fc.weight.data_ptr(), wfc.data_ptr(), self.emb, co, Hf * Wf, 1, st))
+        else:
+            colf = self.ws.get(f"{tag}.colf", (B * flat_dim,))
+            check(lib.ssac_im2col(src.data_ptr(), 0, Hf * Wf * co, 1, Wf * co, co, B, co, Hf, Wf, Hf, 1, 1.0, 0.0,
+                                  colf.data_ptr(), st))
+            wfc = fc.weight
+        if self.big:
+            z = self.ws.get(f"{tag}.z", (B, self.emb))
+            self._fc_forward(colf, wfc, B, flat_dim, z.data_ptr(), self.emb)
+            xhat = self.ws.get(f"{tag}.xhat", (B, self.emb))
+            rstd = self.ws.get(f"{tag}.rstd", (B,))
+            ln = self.module.ln
+            check(lib.ssac_ln_tanh_fwd(z.data_ptr(), self.emb, ln.weight.data_ptr(), ln.bias.data_ptr(), B,
+                                       self.emb, dst_ptr, ld_dst, xhat.data_ptr(), rstd.data_ptr(), st))
+        else:
+            xhat = rstd = None
+            self._fc_forward(colf, wfc, B, flat_dim, dst_ptr, ld_dst)
+        if save:
+            self.saved = dict(B=B, img=img, img_ptr=img_ptr, u8=u8, shape=(Cc, Hh, Ww), fused=fused, cols=cols, ys=ys,
+                              shapes=shapes, colf=colf, wfc=wfc, flat_dim=flat_dim, Hf=Hf, Wf=Wf, xhat=xhat, rstd=rstd,
+                              out=dst, ld_out=ld_dst)
+
+    def _forward_stack(self, img_ptr, shape, u8, tag, save):
+        """both convolutions of a plain two-layer stack in one launch (csrc/ssac_enc_convstack.hip): the first map goes to
+        memory only for backward, the second is written in NCHW flatten order -- the fc's input as its weight is stored"""
+        B, Cc, Hh, Ww = shape
+        (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
+        Hf, Wf = Hh - k1 + 1 - k2 + 1, Ww - k1 + 1 - k2 + 1
+        h1 = self.ws.get("s.h1", (B * co1 * (Hh - k1 + 1) * (Ww - k1 + 1),)) if save else None
+        src = self.ws.get(f"{tag}.flat", (B * co2 * Hf * Wf,))
+        check(lib.ssac_enc_convstack_fwd(img_ptr, u8, self.convs[0].weight.data_ptr(), self.convs[0].bias.data_ptr(),
+                                         self.convs[1].weight.data_ptr(), self.convs[1].bias.data_ptr(), B, Cc, Hh, Ww,
+                                         co1, k1, s1, co2, k2, s2, self.div, self.shift, h1.data_ptr() if save else 0,
+                                         src.data_ptr(), engine.stream()))
+        return [], [h1, src], [], src, Hf, Wf
+
+    def _forward_layers(self, img_ptr, shape, u8, tag, save):
+        """every convolution on its own launches; returns (column matrices, channels-last maps, layer shapes, last map, H, W)"""
+        B, Cc, Hh, Ww = shape
+        st = engine.stream()
         src_ptr = img_ptr
         strides = (Cc * Hh * Ww, Hh * Ww, Ww, 1)
         Hi, Wi, div, shift = Hh, Ww, self.div, self.shift
         cols, ys, shapes = [], [], []
-        tag = "s" if save else "t"
-        fused = self.stack_fused(B, Hh, Ww, save)
-        if fused:
-            # both convolutions in one launch (csrc/ssac_enc_convstack.hip): the first map goes to memory only for backward,
-            # the second is written in NCHW flatten order -- the fc's input as its weight is stored
-            (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
-            Hi, Wi = Hh - k1 + 1 - k2 + 1, Ww - k1 + 1 - k2 + 1
-            h1 = self.ws.get("s.h1", (B * co1 * (Hh - k1 + 1) * (Ww - k1 + 1),)) if save else None
-            src = self.ws.get(f"{tag}.flat", (B * co2 * Hi * Wi,))
-            check(lib.ssac_enc_convstack_fwd(img_ptr, u8, self.convs[0].weight.data_ptr(), self.convs[0].bias.data_ptr(),
-                                             self.convs[1].weight.data_ptr(), self.convs[1].bias.data_ptr(), B, Cc, Hh, Ww,
-                                             co1, k1, s1, co2, k2, s2, div, shift, h1.data_ptr() if save else 0,
-                                             src.data_ptr(), st))
-            ys = [h1, src]
-        for l, (ci, co, k, s) in (() if fused else enumerate(self.geom)):   # (per layer: no pass once the stack ran fused)
+        for l, (ci, co, k, s) in enumerate(self.geom):
             Ho, Wo = (Hi - k) // s + 1, (Wi - k) // s + 1
             rows, ckk = B * Ho * Wo, ci * k * k
             y = self.ws.get(f"{tag}.y{l if save else l % 2}", (rows * co,))
@@ -289,86 +301,43 @@ class ConvEncoderEngine:
             cols.append(col); ys.append(y); shapes.append((ci, co, k, s, Hi, Wi, Ho, Wo))
             src, src_ptr, strides = y, y.data_ptr(), (Ho * Wo * co, 1, Wo * co, co)  # channels-last view of the GEMM output
             Hi, Wi, div, shift = Ho, Wo, 1.0, 0.0
-        co = self.geom[-1][1]
-        flat_dim = co * Hi * Wi
-        fc = self.module.fc
-        if fused:
-            colf, wfc = src, fc.weight
-        elif FC_CHANNELS_LAST:
-            # the last feature map IS the fc input once the weight's columns are put in channels-last order
-            # (emb x C x P -> emb x P x C, 7.8 MB for DrQ: cheaper than gathering B x C*P activations both ways)
-            colf = src
-            wfc = self.ws.get("fc.wcl", (self.emb * flat_dim,))
-            check(lib.ssac_permute_cp(fc.weight.data_ptr(), wfc.data_ptr(), self.emb, co, Hi * Wi, 1, st))
-        else:
-            colf = self.ws.get(f"{tag}.colf", (B * flat_dim,))
-            check(lib.ssac_im2col(src_ptr, 0, *strides, B, co, Hi, Wi, Hi, 1, 1.0, 0.0, colf.data_ptr(), st))
-            wfc = fc.weight
-        fc = self.module.fc
+        return cols, ys, shapes, src, Hi, Wi
 
-        def fc_forward(out_ptr, ld_out):
-            # (B x flat_dim) . (emb x flat_dim)^T: 8 x 1 output tiles only -> cut K into slices so the launch fills
-            # the chip, then a fixed-order reduction adds the bias
-            # few outputs (N <= 64): the operand-stream kernel, one wave per (32 rows, K slice), one workgroup per CU
-            row_groups = (B + 127) // 128
-            skps = ((flat_dim + max(1, 256 // row_groups) - 1) // max(1, 256 // row_groups) + 7) // 8 * 8
-            if FC_STREAM and lib.ssac_linear_fwd_stream_supported(B, self.emb, flat_dim, skps, flat_dim, flat_dim) \
-                    and (flat_dim + skps - 1) // skps >= 4:
-                slices = (flat_dim + skps - 1) // skps
-                part = self.ws.get("fc.partial", (slices * B * self.emb,))
-                check(lib.ssac_linear_fwd_stream(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim, part.data_ptr(), B,
-                                                 self.emb, flat_dim, skps, st))
-                check(lib.ssac_reduce_slices_bias(part.data_ptr(), slices, B, self.emb, fc.bias.data_ptr(), out_ptr,
-                                                  ld_out, st))
-                return
-            kps = max(32, ((flat_dim + FC_SLICES - 1) // FC_SLICES + 31) // 32 * 32)
-            slices = (flat_dim + kps - 1) // kps
-            if slices < 4:
-                check(lib.ssac_linear_fwd(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim,
-                                          fc.bias.data_ptr(), out_ptr, ld_out, B, self.emb, flat_dim, 0, st))
-                return
+    def _fc_forward(self, colf, wfc, B, flat_dim, out_ptr, ld_out):
+        """(B x flat_dim) . (emb x flat_dim)^T: 8 x 1 output tiles only -> cut K into slices so the launch fills the chip,
+        then a fixed-order reduction adds the bias"""
+        fc, st = self.module.fc, engine.stream()
+        # few outputs (N <= 64): the operand-stream kernel, one wave per (32 rows, K slice), one workgroup per CU
+        row_groups = (B + 127) // 128
+        skps = ((flat_dim + max(1, 256 // row_groups) - 1) // max(1, 256 // row_groups) + 7) // 8 * 8
+        if FC_STREAM and lib.ssac_linear_fwd_stream_supported(B, self.emb, flat_dim, skps, flat_dim, flat_dim) \
+                and (flat_dim + skps - 1) // skps >= 4:
+            slices = (flat_dim + skps - 1) // skps
             part = self.ws.get("fc.partial", (slices * B * self.emb,))
-            check(lib.ssac_linear_fwd_splitk(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim,
-                                             part.data_ptr(), B, self.emb, flat_dim, kps, st))
+            check(lib.ssac_linear_fwd_stream(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim, part.data_ptr(), B,
+                                             self.emb, flat_dim, skps, st))
             check(lib.ssac_reduce_slices_bias(part.data_ptr(), slices, B, self.emb, fc.bias.data_ptr(), out_ptr,
                                               ld_out, st))
-        if self.big:
-            z = self.ws.get(f"{tag}.z", (B, self.emb))
-            fc_forward(z.data_ptr(), self.emb)
-            xhat = self.ws.get(f"{tag}.xhat", (B, self.emb))
-            rstd = self.ws.get(f"{tag}.rstd", (B,))
-            ln = self.module.ln
-            check(lib.ssac_ln_tanh_fwd(z.data_ptr(), self.emb, ln.weight.data_ptr(), ln.bias.data_ptr(), B,
-                                       self.emb, dst_ptr, ld_dst, xhat.data_ptr(), rstd.data_ptr(), st))
-        else:
-            xhat = rstd = None
-            fc_forward(dst_ptr, ld_dst)
-        if save:
-            self.saved = dict(B=B, img=img, img_ptr=img_ptr, u8=u8, shape=(Cc, Hh, Ww), fused=fused, cols=cols, ys=ys, shapes=shapes, colf=colf, wfc=wfc, flat_dim=flat_dim,
-                              Hf=Hi, Wf=Wi, xhat=xhat, rstd=rstd, out=dst, ld_out=ld_dst)
+            return
+        kps = max(32, ((flat_dim + FC_SLICES - 1) // FC_SLICES + 31) // 32 * 32)
+        slices = (flat_dim + kps - 1) // kps
+        if slices < 4:
+            check(lib.ssac_linear_fwd(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim,
+                                      fc.bias.data_ptr(), out_ptr, ld_out, B, self.emb, flat_dim, 0, st))
+            return
+        part = self.ws.get("fc.partial", (slices * B * self.emb,))
+        check(lib.ssac_linear_fwd_splitk(colf.data_ptr(), flat_dim, wfc.data_ptr(), flat_dim,
+                                         part.data_ptr(), B, self.emb, flat_dim, kps, st))
+        check(lib.ssac_reduce_slices_bias(part.data_ptr(), slices, B, self.emb, fc.bias.data_ptr(), out_ptr,
+                                          ld_out, st))
 
     # ------------------------------------------------------------------------------------
-    def backward(self, d_rep, accumulate=False):
-        """d_rep (B, emb) contiguous = dL/d(embedding).  Fills self.grads (flat, same layout as the
-        parameters); accumulate=True ADDS to it instead (the members of an ensemble share one encoder and the
-        reference runs ONE backward over the sum of their losses, learning.py:47-121)."""
-        if accumulate:
-            keep, tmp = self.grads, self.__dict__.get("_gtmp")
-            if tmp is None:
-                tmp = self.__dict__["_gtmp"] = torch.zeros_like(self.flat)
-            self.grads = tmp
-            try:
-                self.backward(d_rep)
-            finally:
-                self.grads = keep
-            keep.add_(tmp)   # (device plumbing: one elementwise pass over the gradient arena)
-            return
+    def _backward(self, d_rep):
         sv = self.saved
         assert sv is not None, "backward() needs a forward(save=True)"
         B, st = sv["B"], engine.stream()
-        nconv = len(self.geom)
-        k_fcw, k_fcb = 2 * nconv, 2 * nconv + 1
         if self.big:
+            k_fcb = 2 * len(self.geom) + 1
             dz = self.ws.get("b.dz", (B, self.emb))
             scratch = self.ws.get("b.lnscratch", (B, self.emb))
             check(lib.ssac_ln_tanh_bwd(d_rep.data_ptr(), self.emb, sv["out"].data_ptr(), sv["ld_out"],
@@ -378,26 +347,37 @@ class ConvEncoderEngine:
                                        self._seg(k_fcb + 2, self.grads).data_ptr(), st))
         else:
             dz = d_rep
-        flat_dim = sv["flat_dim"]
         if sv["fused"]:
-            # fc on the NCHW flatten as it is stored: weight gradient straight into the arena, backward-data, then both
-            # layers' gradients as one partial per image tile, summed in a fixed order into the arena's first four tensors
-            (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
-            Cc, Hh, Ww = sv["shape"]
-            check(lib.ssac_linear_wgrad_splitk(dz.data_ptr(), self.emb, sv["colf"].data_ptr(), flat_dim,
-                                               self._seg(k_fcw, self.grads).data_ptr(),
-                                               self._seg(k_fcb, self.grads).data_ptr(), self.emb, flat_dim, B, B, st))
-            dflat = self.ws.get("b.dflat", (B * flat_dim,))
-            check(lib.ssac_linear_dgrad(dz.data_ptr(), self.emb, self.module.fc.weight.data_ptr(), flat_dim,
-                                        dflat.data_ptr(), flat_dim, B, flat_dim, self.emb, st))
-            slices, n = (B + STACK_TILE - 1) // STACK_TILE, self.offs[4]
-            assert n == co1 * (ci * k1 * k1 + 1) + co2 * (co1 * k2 * k2 + 1)   # (the four tensors lie back to back)
-            part = self.ws.get("b.pstack", (slices * n,))
-            check(lib.ssac_enc_convstack_bwd(dflat.data_ptr(), sv["img_ptr"], sv["u8"], sv["ys"][0].data_ptr(),
-                                             sv["ys"][1].data_ptr(), self.convs[1].weight.data_ptr(), B, Cc, Hh, Ww, co1, k1,
-                                             s1, co2, k2, s2, self.div, self.shift, part.data_ptr(), st))
-            check(lib.ssac_reduce_slices(part.data_ptr(), slices, n, self.grads.data_ptr(), st))
-            return
+            self._backward_stack(dz, sv)
+        else:
+            self._backward_layers(self._backward_fc(dz, sv), sv)
+
+    def _backward_stack(self, dz, sv):
+        """fc on the NCHW flatten as it is stored: weight gradient straight into the arena, backward-data, then both layers'
+        gradients as one partial per image tile, summed in a fixed order into the arena's first four tensors"""
+        B, flat_dim, st = sv["B"], sv["flat_dim"], engine.stream()
+        k_fcw, k_fcb = 2 * len(self.geom), 2 * len(self.geom) + 1
+        (ci, co1, k1, s1), (_, co2, k2, s2) = self.geom
+        Cc, Hh, Ww = sv["shape"]
+        check(lib.ssac_linear_wgrad_splitk(dz.data_ptr(), self.emb, sv["colf"].data_ptr(), flat_dim,
+                                           self._seg(k_fcw, self.grads).data_ptr(),
+                                           self._seg(k_fcb, self.grads).data_ptr(), self.emb, flat_dim, B, B, st))
+        dflat = self.ws.get("b.dflat", (B * flat_dim,))
+        check(lib.ssac_linear_dgrad(dz.data_ptr(), self.emb, self.module.fc.weight.data_ptr(), flat_dim,
+                                    dflat.data_ptr(), flat_dim, B, flat_dim, self.emb, st))
+        slices, n = (B + STACK_TILE - 1) // STACK_TILE, self.offs[4]
+        assert n == co1 * (ci * k1 * k1 + 1) + co2 * (co1 * k2 * k2 + 1)   # (the four tensors lie back to back)
+        part = self.ws.get("b.pstack", (slices * n,))
+        check(lib.ssac_enc_convstack_bwd(dflat.data_ptr(), sv["img_ptr"], sv["u8"], sv["ys"][0].data_ptr(),
+                                         sv["ys"][1].data_ptr(), self.convs[1].weight.data_ptr(), B, Cc, Hh, Ww, co1, k1,
+                                         s1, co2, k2, s2, self.div, self.shift, part.data_ptr(), st))
+        check(lib.ssac_reduce_slices(part.data_ptr(), slices, n, self.grads.data_ptr(), st))
+
+    def _backward_fc(self, dz, sv):
+        """the fc layer's gradients into the arena; returns dL/d(last map), masked by its ReLU, channels-last"""
+        B, flat_dim, st = sv["B"], sv["flat_dim"], engine.stream()
+        nconv = len(self.geom)
+        k_fcw, k_fcb = 2 * nconv, 2 * nconv + 1
         ci, co, k, s, Hi, Wi, Ho, Wo = sv["shapes"][-1]
         dy = self.ws.get(f"b.dy{(nconv - 1) % 2}", (B * Ho * Wo * co,))
         ylast = sv["ys"][-1]
@@ -424,7 +404,12 @@ class ConvEncoderEngine:
             cl = (Ho * Wo * co, 1, Wo * co, co)
             check(lib.ssac_col2im(dcolf.data_ptr(), dy.data_ptr(), *cl, ylast.data_ptr(), *cl, B, co, Ho, Wo,
                                   sv["Hf"], 1, st))
-        for l in range(nconv - 1, -1, -1):
+        return dy
+
+    def _backward_layers(self, dy, sv):
+        """down the convolutions: weight gradient (slices reduced in a fixed order), then backward-data, layer by layer"""
+        B, st = sv["B"], engine.stream()
+        for l in range(len(self.geom) - 1, -1, -1):
             ci, co, k, s, Hi, Wi, Ho, Wo = sv["shapes"][l]
             rows, ckk = B * Ho * Wo, ci * k * k
             first = l == 0 and self.first
@@ -491,34 +476,11 @@ class ConvEncoderEngine:
                                           B, ci, Hi, Wi, k, s, st))
             dy = dprev
 
-    # ------------------------------------------------------------------------------------
-    def optimizer_step(self, optimizer, clip, norm_out=None, step=True):
-        """clip_grad_norm_(encoder.parameters(), clip) + encoder_optimizer.step() (learning.py:127-129).
-        step=False: clip and log only (offline_actor_update without update_encoder, learning.py:203-208)."""
-        st = engine.stream()
-        adam = engine.adam_group(optimizer, self.device)
-        if step:
-            adam.advance()
-        nb = int(lib.ssac_sumsq_blocks())
-        ss = self.ws.get("o.ss", (nb,))
-        check(lib.ssac_sumsq(self.grads.data_ptr(), self.numel, ss.data_ptr(), st))
-        check(lib.ssac_clip_coef(adam.ctl.ptr, ss.data_ptr(), nb, float(clip) if clip else 0.0, 0, st))
-        if norm_out is not None:
-            check(lib.ssac_group_norms(ss.data_ptr(), 1, nb, adam.ctl.ptr, norm_out.data_ptr(), st))
-        if not step:
-            return
-        m, v = adam.moments_for(self.moments_key, self.flat)
-        check(lib.ssac_adam_step(self.flat.data_ptr(), m.data_ptr(), v.data_ptr(), self.grads.data_ptr(),
-                                 self.numel, adam.ctl.ptr, st))
-
 
 def conv_engine(encoder, device):
-    """ConvEncoderEngine of `encoder` (cached on the wrapped conv module; re-packed after a deepcopy)."""
+    """ConvEncoderEngine of `encoder` (cached on the wrapped conv module under encoder_base.cached_engine's rule), or None
+    when it holds no convolutional module"""
     mod = find_conv_module(encoder)
     if mod is None:
         return None
-    eng = mod.__dict__.get("_ssac_conv")
-    if eng is None or eng.module is not mod or not eng.is_bound() or eng.device != device:
-        eng = ConvEncoderEngine(mod, device)
-        mod.__dict__["_ssac_conv"] = eng
-    return eng
+    return cached_engine(mod, "_ssac_conv", device, lambda dev: ConvEncoderEngine(mod, dev))

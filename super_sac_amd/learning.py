@@ -16,7 +16,7 @@ import types
 import numpy as np
 import torch
 
-from . import beta, engine, mlp_encoder, parallel, rng
+from . import beta, encoder_base, engine, parallel, rng
 from . import learning_utils as lu
 from . import _lib
 from ._lib import check, lib
@@ -127,7 +127,7 @@ def _encoder_step(encoder, encoder_optimizer, encoder_clip, dX, emb, ws, slot, d
     inv = (as_rep, os_rep, encoder_lambda, stacked): the encoder invariance constraint (learning.py:114-117) adds
     lambda * d||as_rep - os_rep||_F / d as_rep -- to the critics' rows when the augmented batch IS the critic batch,
     to rows [B, 2B) of a stacked pass otherwise."""
-    eng = mlp_encoder.encoder_engine(encoder, dev)
+    eng = encoder_base.encoder_engine(encoder, dev)
     B = dX.shape[1]
     stacked = inv is not None and inv[3]
     d_rep = ws.get("cu.drep2" if stacked else "cu.drep", (2 * B if stacked else B, emb))
@@ -289,7 +289,7 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
             return fs.run()
     lu.ensure_adopted(agent, buffer)
     lu.ensure_adopted(target_agent, buffer)
-    mlp_encoder.refuse_unsupported(agent, "critic_update", encoder_lambda=encoder_lambda)
+    encoder_base.refuse_unsupported(agent, "critic_update", encoder_lambda=encoder_lambda)
     shard = parallel.shard_of(agent)
     is_beta = lu.actor_kind(agent.actors[0]) == "beta"
     if is_beta and (shard is not None or parallel.member_shard_of(agent) is not None):
@@ -777,12 +777,7 @@ def _encoder_input(m, c):
         # encoder invariance on a partly augmented batch: the fully augmented observations need an encoder
         # pass of their own WITH gradient -- one stacked 2B-row pass [o ; ao], whose backward then receives
         # the critics' gradient in rows [0, B) and the constraint's in rows [B, 2B)
-        eng = mlp_encoder.encoder_engine(agent.encoder, c.dev)
-        img2 = ws.get("cu.img2", (2 * B,) + tuple(o[okey].shape[1:]))
-        img2[:B].copy_(o[okey])
-        img2[B:].copy_(rd["augmented_obs"][0][okey])
-        sall = ws.get("cu.sall", (2 * B, eng.emb))
-        eng.forward(img2, sall, eng.emb, True)
+        eng, sall = lu.encode_stacked(agent.encoder, o, rd["augmented_obs"][0], ws, "cu.img2", c.dev)
         xin[:, :eng.emb].copy_(sall[:B])
         s_rep, as_rep, stacked = xin[:, :eng.emb], sall[B:], True
     else:
@@ -1066,7 +1061,7 @@ def online_actor_update(buffer, agent, pop, actor_optimizer, log_alphas, batch_s
     _online_actor_update all read its answer."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
-    mlp_encoder.refuse_unsupported(agent, "online_actor_update")
+    encoder_base.refuse_unsupported(agent, "online_actor_update")
     kw = dict(buffer=buffer, agent=agent, pop=pop, actor_optimizer=actor_optimizer, log_alphas=log_alphas,
               batch_size=batch_size, clip=clip, random_process=random_process, noise_clip=noise_clip,
               augmenter=augmenter, aug_mix=aug_mix, premade_replay_dicts=premade_replay_dicts, per=per,
@@ -1438,7 +1433,7 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
     prioritised batch whose priorities are refreshed from the advantage afterwards."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
-    mlp_encoder.refuse_unsupported(agent, "offline_actor_update", actor_lambda=actor_lambda)
+    encoder_base.refuse_unsupported(agent, "offline_actor_update", actor_lambda=actor_lambda)
     if not discrete and lu.actor_kind(agent.actors[0]) == "beta":
         if filter_:
             beta.refuse("offline_actor_update with the advantage filter (filter_=True)")
@@ -1505,13 +1500,7 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
             # (2) the BC rows and the AUGMENTED rows go through the encoder / actor as ONE stacked 2B-row pass: their
             #     weight gradients add up inside one backward
             if pixel:
-                okey = getattr(agent.encoder, "ssac_obs_key", "obs")
-                eng = mlp_encoder.encoder_engine(agent.encoder, dev)
-                img2 = ws.get("bc.img2", (2 * B,) + tuple(o[okey].shape[1:]))
-                img2[:B].copy_(o[okey])
-                img2[B:].copy_(ao[okey])
-                X2 = ws.get("bc.sall", (2 * B, eng.emb))
-                eng.forward(img2, X2, eng.emb, True)
+                eng, X2 = lu.encode_stacked(agent.encoder, o, ao, ws, "bc.img2", dev)
             else:
                 s_rep, as_rep = lu.encode(agent.encoder, o), lu.encode(agent.encoder, ao)
                 X2 = ws.get("bc.x2", (2 * B, s_rep.shape[1]))
@@ -1600,7 +1589,7 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
     ssac_bc_discrete_bwd (log-probability of the data action), ssac_bce_sigmoid_bwd, ssac_markov_smoothness_bwd."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
-    mlp_encoder.refuse_unsupported(agent, "markov_state_abstraction_update")
+    encoder_base.refuse_unsupported(agent, "markov_state_abstraction_update")
     if not discrete and getattr(agent.inverse_model, "dist_impl", None) == "beta":
         beta.refuse("markov_state_abstraction_update with a Beta inverse model")
     inv, con = agent.inverse_model, agent.contrastive_model
@@ -1614,21 +1603,12 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
     o, a, _, o1, _ = rd["primary_batch"]
     B = batch_size
     ident = lu.is_identity(agent.encoder)
-    eng = None
     if ident:
         s_rep, s1_rep = lu.encode(agent.encoder, o), lu.encode(agent.encoder, o1)
         D = s_rep.shape[1]
     else:
-        eng = mlp_encoder.encoder_engine(agent.encoder, dev, o)
-        key = getattr(agent.encoder, "ssac_obs_key", "obs")
-        if eng is None:
-            raise NotImplementedError(f"{type(agent.encoder).__name__}: this encoder has no HIP path")
+        eng, s_all = lu.encode_stacked(agent.encoder, o, o1, ws, "mk.img", dev)
         D = eng.emb
-        img = ws.get("mk.img", (2 * B,) + tuple(o[key].shape[1:]))
-        img[:B].copy_(o[key])
-        img[B:].copy_(o1[key])   # (device plumbing: the two observation batches behind one another)
-        s_all = ws.get("mk.sall", (2 * B, D))
-        eng.forward(img, s_all, D, True)
         s_rep, s1_rep = s_all[:B], s_all[B:]
     # ---- inputs: [s | s'] for the inverse model; [s | s'] over [s | s'[perm]] for the contrastive model
     perm = rng.draw_permutation(B)
@@ -1692,7 +1672,7 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
         d_all[B:].index_add_(0, perm_dev, dxc[B:, D:])  # (a permutation: every row receives exactly one addend)
         eng.backward(d_all)
         ss_enc = ws.get("mk.enc.ss", (int(lib.ssac_sumsq_blocks()),))
-        check(lib.ssac_sumsq(eng.grads.data_ptr(), eng.numel, ss_enc.data_ptr(), st))
+        eng.grad_sumsq(ss_enc)
         allss.append(ss_enc)
     # ---- clip_grad_norm_ over chain(encoder, inverse, contrastive) jointly, then optimizer.step() (learning.py:321-330)
     cat = torch.cat(allss)
@@ -1703,9 +1683,7 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
                                  arena.params.numel(), adam.ctl.ptr, st))
         arena.sync_shadow()
     if not ident:
-        m, v = adam.moments_for(eng.moments_key, eng.flat)
-        check(lib.ssac_adam_step(eng.flat.data_ptr(), m.data_ptr(), v.data_ptr(), eng.grads.data_ptr(), eng.numel,
-                                 adam.ctl.ptr, st))
+        eng.adam_step(adam)
     # ---- logs (learning.py:332-340): the norms are read after the clip rescaled the gradients
     scale = adam.ctl.ptr if grad_clip else 0
     for (arena, _, _, ss, _), off in zip(members, (lu.L_MK_GN_INV, lu.L_MK_GN_CON)):
@@ -1725,7 +1703,7 @@ def alpha_update(buffer, agent, optimizers, batch_size, log_alphas, augmenter, a
                  premade_replay_dicts, discrete):
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
-    mlp_encoder.refuse_unsupported(agent, "alpha_update")
+    encoder_base.refuse_unsupported(agent, "alpha_update")
     dev = log_alphas[0].device
     ws = lu.agent_ws(agent, dev)
     if engine.CAPTURE is None:

@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from . import augmentations, beta, engine, nets, rng
+from . import augmentations, beta, encoder_base, engine, nets, rng
 from . import _lib
 from ._lib import check, lib
 
@@ -487,15 +487,27 @@ def encode(encoder, obs_dict, dst=None, save=False):
     key = getattr(encoder, "ssac_identity_key", None)
     if key is not None:
         return obs_dict[key]
-    from . import mlp_encoder
-    eng = mlp_encoder.encoder_engine(encoder, next(iter(obs_dict.values())).device, obs_dict)
-    if eng is None:
-        raise NotImplementedError(f"{type(encoder).__name__}: this encoder has no HIP path")
+    eng = encoder_base.require_engine(encoder, next(iter(obs_dict.values())).device, obs_dict)
     img = obs_dict[getattr(encoder, "ssac_obs_key", "obs")]
     if dst is None:
         dst = torch.empty(img.shape[0], eng.emb, device=img.device)
     eng.forward(img, dst, dst.stride(0), save)
     return dst[:, :eng.emb]
+
+
+def encode_stacked(encoder, first, second, ws, tag, dev):
+    """two B-row observation batches as ONE 2B-row encoder pass that keeps what backward() needs (`first` in rows [0, B),
+    `second` in [B, 2B): the weight gradients of both uses add up inside one backward).  The observations go to the
+    workspace buffer `tag` ("cu.img2"), the embeddings to "<tag's prefix>.sall"; returns (engine, embeddings)."""
+    eng = encoder_base.require_engine(encoder, dev, first)
+    key = getattr(encoder, "ssac_obs_key", "obs")
+    B = first[key].shape[0]
+    img = ws.get(tag, (2 * B,) + tuple(first[key].shape[1:]))
+    img[:B].copy_(first[key])
+    img[B:].copy_(second[key])   # (device plumbing: the two observation batches behind one another)
+    sall = ws.get(tag.partition(".")[0] + ".sall", (2 * B, eng.emb))
+    eng.forward(img, sall, eng.emb, True)
+    return eng, sall
 
 
 def is_identity(encoder):

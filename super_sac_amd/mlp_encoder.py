@@ -4,9 +4,9 @@ Linear(128, dim) -> ReLU) and ``VisgridEncoder`` (experiments/visgrid/train.py: 
 Linear(256, 2) -> tanh), and ``nets.MlpEncoder``.
 
 ``find_mlp_encoder`` recognises such a module by its structure (exactly two ``nn.Linear``) and confirms the FUNCTION by
-probing it once on a few random rows (the precedent is ``adopt.probe_identity``); ``MlpEncoderEngine`` has the interface of
-``conv_encoder.ConvEncoderEngine`` -- ``emb``, ``forward``, ``forward_ptr``, ``backward``, ``optimizer_step``, ``flat`` /
-``grads`` / ``is_bound`` -- so the update functions only look the engine up through ``encoder_engine``.
+probing it once on a few random rows (the precedent is ``adopt.probe_identity``); ``MlpEncoderEngine`` is an
+``encoder_base.EncoderEngine`` like the convolution engine, so the update functions only look the engine up
+(``encoder_base.encoder_engine``).
 
 Two forms, switched by ``USE_FUSED`` (the tests' A/B, not user configuration):
     per layer   ssac_linear_fwd twice + ssac_enc_act_fwd; ssac_enc_act_bwd, ssac_linear_dgrad_masked and the split-K
@@ -20,6 +20,7 @@ from torch import nn
 
 from . import engine
 from ._lib import check, lib
+from .encoder_base import EncoderEngine, arena_layout, cached_engine  # noqa: F401  (arena_layout stays importable here)
 
 # True: ssac_enc_mlp2_fwd where ssac_enc_mlp2_supported says it measured faster than the per-layer launches
 # (profiles/mlp_encoder.md); False: every layer on its own launches; "all": both fused launches, forward AND backward,
@@ -135,43 +136,16 @@ def find_mlp_encoder(encoder, obs_dict=None):
     return desc or None
 
 
-def arena_layout(numels):
-    """offsets (each a multiple of 4 floats) and the total length of a flat arena holding tensors of `numels` elements"""
-    offs, o = [], 0
-    for n in numels:
-        offs.append(o)
-        o += (n + 3) // 4 * 4
-    return offs, o
+class MlpEncoderEngine(EncoderEngine):
+    moments_key = "mlp_encoder"
 
-
-class MlpEncoderEngine:
     def __init__(self, encoder, desc, device):
         self.module = encoder
-        self.device = torch.device(device)
         self.lin0, self.lin1, self.act_name, self.key = desc
         self.act2 = ACTS[self.act_name]
         self.K, self.H, self.emb = self.lin0.in_features, self.lin0.out_features, self.lin1.out_features
-        # ---- flat parameter arena (each tensor starts at a multiple of 4 floats); the base class's dummy Linear(1, 1)
-        #      never receives a gradient (torch's Adam skips it) and stays outside
-        self.plist = [self.lin0.weight, self.lin0.bias, self.lin1.weight, self.lin1.bias]
-        self.offs, self.numel = arena_layout([p.numel() for p in self.plist])
-        self.flat = torch.zeros(self.numel, dtype=torch.float32, device=device)
-        with torch.no_grad():
-            for p, off in zip(self.plist, self.offs):
-                v = self.flat[off:off + p.numel()].view(p.shape)
-                v.copy_(p.data.to(device=device, dtype=torch.float32))
-                p.data = v
-        self.grads = torch.zeros_like(self.flat)
-        self.moments_key = "mlp_encoder"
-        self.ws = engine.Workspace(device) if self.device.type == "cuda" else None
-        self.saved = None
-
-    def is_bound(self):
-        return all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(self.plist, self.offs))
-
-    def _seg(self, k, tensor=None):
-        t = self.flat if tensor is None else tensor
-        return t[self.offs[k]:self.offs[k] + self.plist[k].numel()]
+        # the base class's dummy Linear(1, 1) never receives a gradient (torch's Adam skips it) and stays outside the arena
+        self._pack([self.lin0.weight, self.lin0.bias, self.lin1.weight, self.lin1.bias], device)
 
     def fused(self, M):
         """the forward of an M-row batch takes the fused launch"""
@@ -244,21 +218,7 @@ class MlpEncoderEngine:
         check(lib.ssac_reduce_slices_pair(pw.data_ptr(), n_out * n_in, gw.data_ptr(), pb.data_ptr(), n_out, gb.data_ptr(),
                                           slices, st))
 
-    def backward(self, d_rep, accumulate=False):
-        """d_rep (B, emb) contiguous = dL/d(embedding).  Fills self.grads (flat, same layout as the parameters);
-        accumulate=True ADDS to it instead (the members of an ensemble share one encoder and the reference runs ONE
-        backward over the sum of their losses)."""
-        if accumulate:
-            keep, tmp = self.grads, self.__dict__.get("_gtmp")
-            if tmp is None:
-                tmp = self.__dict__["_gtmp"] = torch.zeros_like(self.flat)
-            self.grads = tmp
-            try:
-                self.backward(d_rep)
-            finally:
-                self.grads = keep
-            keep.add_(tmp)   # (device plumbing: one elementwise pass over the gradient arena)
-            return
+    def _backward(self, d_rep):
         sv = self.saved
         assert sv is not None, "backward() needs a forward(save=True)"
         B, st = sv["B"], engine.stream()
@@ -278,73 +238,16 @@ class MlpEncoderEngine:
         self._wgrad(dz1, N, h.data_ptr(), H, N, H, B, 2, 3, st)
         self._wgrad(dz0, H, sv["x_ptr"], sv["ldx"], H, K, B, 0, 1, st)
 
-    # ------------------------------------------------------------------------------------
-    def optimizer_step(self, optimizer, clip, norm_out=None, step=True):
-        """clip_grad_norm_(encoder.parameters(), clip) + encoder_optimizer.step() (learning.py:127-129).
-        step=False: clip and log only (offline_actor_update without update_encoder, learning.py:203-208)."""
-        st = engine.stream()
-        adam = engine.adam_group(optimizer, self.device)
-        if step:
-            adam.advance()
-        nb = int(lib.ssac_sumsq_blocks())
-        ss = self.ws.get("o.ss", (nb,))
-        check(lib.ssac_sumsq(self.grads.data_ptr(), self.numel, ss.data_ptr(), st))
-        check(lib.ssac_clip_coef(adam.ctl.ptr, ss.data_ptr(), nb, float(clip) if clip else 0.0, 0, st))
-        if norm_out is not None:
-            check(lib.ssac_group_norms(ss.data_ptr(), 1, nb, adam.ctl.ptr, norm_out.data_ptr(), st))
-        if not step:
-            return
-        m, v = adam.moments_for(self.moments_key, self.flat)
-        check(lib.ssac_adam_step(self.flat.data_ptr(), m.data_ptr(), v.data_ptr(), self.grads.data_ptr(),
-                                 self.numel, adam.ctl.ptr, st))
-
 
 def mlp_engine(encoder, device, obs_dict=None):
-    """MlpEncoderEngine of `encoder` (cached on the encoder; re-packed after a deepcopy, a device change or anything else
-    that moved the parameters out of the arena), or None when it is no two-layer MLP encoder"""
+    """MlpEncoderEngine of `encoder` (cached on the encoder under encoder_base.cached_engine's rule), or None when it is no
+    two-layer MLP encoder"""
     desc = find_mlp_encoder(encoder, obs_dict)
     if desc is None:
         return None
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:   # ("cuda" and "cuda:0" name one device: one engine)
-        device = torch.device("cuda", torch.cuda.current_device())
-    eng = encoder.__dict__.get("_ssac_mlp")
-    if eng is None or eng.module is not encoder or eng.device != device or not eng.is_bound():
-        eng = MlpEncoderEngine(encoder, desc, device)
-        encoder.__dict__["_ssac_mlp"] = eng
-    return eng
+    return cached_engine(encoder, "_ssac_mlp", device, lambda dev: MlpEncoderEngine(encoder, desc, dev))
 
 
 def is_mlp_encoder(encoder):
     """recognised already (no probe here: an encoder nobody has looked at yet answers False)"""
     return bool(isinstance(encoder, nn.Module) and encoder.__dict__.get("_ssac_mlp_desc"))
-
-
-def refuse_unsupported(agent, where, encoder_lambda=0.0, actor_lambda=0.0):
-    """what an agent with an MLP encoder cannot ask of `where` (an update function's name), each with its reason"""
-    if not is_mlp_encoder(agent.encoder):   # (learning_utils.ensure_adopted has looked at the encoder by now)
-        return
-    name = type(agent.encoder).__name__
-    if encoder_lambda or actor_lambda:
-        which = "encoder_lambda" if encoder_lambda else "actor_lambda"
-        raise NotImplementedError(
-            f"{where}: {which} != 0 with the MLP encoder {name}: vector observations have only the identity augmentation, "
-            "so the reference's invariance constraint is the norm of a zero tensor; pass 0")
-    if any(o.__dict__.get("_ssac_precision") == "bf16" for o in list(agent.actors) + list(agent.critics)):
-        raise NotImplementedError(
-            f"{where}: set_precision('bf16') with the MLP encoder {name}: the bf16 operand mode covers agents whose encoder "
-            "is an identity")
-    from . import parallel
-    if parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None:
-        raise NotImplementedError(
-            f"{where}: critic- or member-sharded agents with the MLP encoder {name}: a trainable encoder is shared by all "
-            "members and is not sharded (trainable pixel encoders are refused likewise)")
-
-
-def encoder_engine(encoder, device, obs_dict=None):
-    """the engine behind a trainable encoder: the convolution engine (conv_encoder.py) or the MLP engine, else None"""
-    from . import conv_encoder
-    eng = conv_encoder.conv_engine(encoder, device)
-    if eng is not None:
-        return eng
-    return mlp_engine(encoder, device, obs_dict)

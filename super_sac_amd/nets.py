@@ -13,6 +13,7 @@ from torch import nn
 
 from . import engine
 from ._lib import check, lib
+from .encoder_base import module_forward
 
 
 def weight_init(m):
@@ -189,27 +190,14 @@ class MlpEncoder(Encoder):
         return self._dim
 
     def forward(self, obs_dict):
-        from . import mlp_encoder
-        x = obs_dict[self.ssac_obs_key]
-        engine.require_gpu(x)
-        eng = mlp_encoder.mlp_engine(self, x.device)
-        out = torch.empty(x.shape[0], self._dim, device=x.device)
-        eng.forward(x.float(), out, self._dim, save=False)
-        return out
+        return module_forward(self, obs_dict[self.ssac_obs_key].float())
 
 
 class _PixelEncoderBase(nn.Module):
     """parameter container of a convolutional encoder; arithmetic lives in conv_encoder.py"""
 
     def forward(self, obs):
-        from . import conv_encoder
-        engine.require_gpu(obs)
-        eng = conv_encoder.ConvEncoderEngine(self, obs.device) if "_ssac_conv" not in self.__dict__ \
-            else self.__dict__["_ssac_conv"]
-        self.__dict__["_ssac_conv"] = eng
-        out = torch.empty(obs.shape[0], self.embedding_dim, device=obs.device)
-        eng.forward(obs.float(), out, self.embedding_dim, save=False)
-        return out
+        return module_forward(self, obs.float())
 
 
 def _conv_out(n, k, s):
@@ -277,13 +265,8 @@ class ConvStackEncoder(Encoder):
         return self._dim
 
     def forward(self, obs_dict):
-        from . import conv_encoder
         x = obs_dict[self.ssac_obs_key]
-        engine.require_gpu(x)
-        eng = conv_encoder.conv_engine(self, x.device)
-        out = torch.empty(x.shape[0], self._dim, device=x.device)
-        eng.forward(x if x.dtype == torch.uint8 else x.float(), out, self._dim, save=False)
-        return out
+        return module_forward(self, x if x.dtype == torch.uint8 else x.float())
 
 
 class PixelEncoder(Encoder):

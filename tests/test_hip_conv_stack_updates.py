@@ -168,3 +168,39 @@ def test_bf16_and_sharded_agents_are_refused_as_for_pixel_encoders(orc):
     sharded.agent.ssac_member_shard = types.SimpleNamespace(ensemble_size=2, lo=0, hi=1)   # (what parallel.install leaves)
     with pytest.raises(AssertionError, match="a trainable encoder is shared by all members"):
         ssa.learning.critic_update(**_critic_kwargs(sharded))
+
+
+def test_the_spelling_of_the_device_does_not_repack_the_engine():
+    """"cuda" and "cuda:<current>" name one device: one engine, one arena"""
+    import super_sac_amd as ssa
+    from super_sac_amd import conv_encoder as ce
+    enc = ssa.nets.ConvStackEncoder((4, 10, 10)).cuda()
+    x = (torch.rand(32, 4, 10, 10, generator=torch.Generator().manual_seed(1)) < 0.3).to(torch.uint8).cuda()
+    eng = ce.conv_engine(enc, torch.device("cuda"))
+    ptr, out = eng.flat.data_ptr(), enc({"obs": x})
+    indexed = ce.conv_engine(enc, torch.device("cuda", torch.cuda.current_device()))
+    assert indexed is eng and indexed.flat.data_ptr() == ptr and eng.is_bound()
+    assert ce.conv_engine(enc, torch.device("cuda")) is eng and ce.conv_engine(enc, "cuda") is eng
+    assert enc.__dict__["_ssac_conv"] is eng and torch.equal(enc({"obs": x}), out)
+
+
+def test_a_copied_pixel_encoder_forwards_through_an_engine_of_its_own():
+    """copy.deepcopy clones the parameters out of the arena and copies the cache slot: the twin's forward re-packs instead
+    of running the engine the parameters left"""
+    import super_sac_amd as ssa
+    conv = ssa.nets.SmallPixelEncoder((4, 36, 36)).cuda()
+    x = torch.randint(0, 256, (2, 4, 36, 36), generator=torch.Generator().manual_seed(2)).float().cuda()
+    out = conv(x)
+    eng = conv.__dict__["_ssac_conv"]
+    twin = copy.deepcopy(conv)
+    assert torch.equal(twin(x), out)
+    teng = twin.__dict__["_ssac_conv"]
+    assert teng is not eng and teng.module is twin and teng.is_bound() and eng.is_bound()
+    assert teng.flat.data_ptr() != eng.flat.data_ptr()
+    with torch.no_grad():
+        twin.fc.bias.add_(1.0)
+        twin.conv1.weight.mul_(0.5)
+    moved = twin(x)
+    assert teng.is_bound() and twin.__dict__["_ssac_conv"] is teng
+    assert torch.equal(teng._seg(len(teng.plist) - 1), twin.fc.bias.detach()) and not torch.equal(moved, out)
+    assert torch.equal(conv(x), out), "the original answers as before"
