@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 12
+#define SSAC_ABI_VERSION 13
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -1048,6 +1048,22 @@ int ssac_enc_mlp2_fwd(const float *X, int64_t ldx, const float *W0, const float 
                       int M, int K, int H, int N, int act2, float *H_save, float *Y, int64_t ldy, void *stream);
 int ssac_enc_mlp2_bwd(const float *dY, int64_t ldd, const float *Y, int64_t ldy, const float *H_save, const float *W1,
                       int M, int H, int N, int act2, float *dZ1, float *dZ0, void *stream);
+/* The forward of a few rows (an acting call), without H_save: Y[:, :N] = act2(relu(X W0^T + b0) W1^T + b1), exact fp32 (fmaf
+ * chains), bias and activation separate operations.  No MFMA tile: layer 1 runs on H / 4 workgroups, a wave per hidden unit
+ * with K split over its lanes and a fixed shuffle tree; layer 2 is computed by the LAST workgroup to arrive (a fence and one
+ * atomic add on an arrival counter; no workgroup ever waits for another).  Every output element has one owner and one
+ * summation order, fixed by the shape alone: a replay is bit-identical.
+ * Covered (ssac_enc_mlp2_rows_covered): 1 <= M <= 16; H % 32 == 0, 32 <= H <= 256; 1 <= K <= 512; 1 <= N <= 65536; any
+ * ldx >= K, ldy >= N, any pointer alignment; the launch refuses everything else.  ssac_enc_mlp2_rows_supported: covered AND
+ * measured faster than the launches an acting plan records otherwise (profiles/mlp_encoder.md, "Acting").
+ * scratch: SSAC_ENC_ROWS_SCRATCH floats, zeroed ONCE by the caller and then left to the launches (word 0 is the arrival
+ * counter, which every launch returns to zero; the hidden rows follow); launches sharing a scratch block must be ordered
+ * on one stream. */
+#define SSAC_ENC_ROWS_SCRATCH (4 + 16 * 256)
+int ssac_enc_mlp2_rows_covered(int M, int K, int H, int N);
+int ssac_enc_mlp2_rows_supported(int M, int K, int H, int N);
+int ssac_enc_mlp2_fwd_rows(const float *X, int64_t ldx, const float *W0, const float *b0, const float *W1, const float *b1,
+                           int M, int K, int H, int N, int act2, float *Y, int64_t ldy, float *scratch, void *stream);
 
 /* ==== plain two-layer convolution stacks on small maps (csrc/ssac_enc_convstack.hip): the reference's MinAtar encoder
  * (experiments/minatar/minatar_utils.py:37-63) ahead of its fc:

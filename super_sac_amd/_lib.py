@@ -221,6 +221,9 @@ SIGNATURES = {
     "ssac_enc_mlp2_supported": [_I, _I, _I, _I],
     "ssac_enc_mlp2_fwd": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P],
     "ssac_enc_mlp2_bwd": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "ssac_enc_mlp2_rows_covered": [_I, _I, _I, _I],
+    "ssac_enc_mlp2_rows_supported": [_I, _I, _I, _I],
+    "ssac_enc_mlp2_fwd_rows": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P],
     "ssac_enc_convstack_covered": [_I] * 9,
     "ssac_enc_convstack_supported": [_I] * 10,
     "ssac_enc_convstack_fwd": [_P, _I, _P, _P, _P, _P] + [_I] * 10 + [_F, _F, _P, _P, _P],
@@ -312,7 +315,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def _load():

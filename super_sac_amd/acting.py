@@ -1,7 +1,7 @@
 """The acting path as ONE C call per environment step (agent.py:204-315; csrc/ssac_act.hip).
 
-``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent, or of a pixel-encoder agent
-on uint8 or float32 frames, take this path: the first call at a given (rule, num_envs) RECORDS the rule's launches -- every actor's
+``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent, of a pixel-encoder agent
+on uint8 or float32 frames, or of an agent with a two-layer MLP encoder (below), take this path: the first call at a given (rule, num_envs) RECORDS the rule's launches -- every actor's
 forward (+ tanh-normal sample from the engine's Philox stream, in the kernel), SUNRISE's ensemble-Q passes on the stacked
 candidates, the rule's reduction (UCB arg-max / mean of mean actions / categorical draw / arg-max of mean probabilities) and
 the publish step -- into a launch list of an ``ssac_act`` plan; every later call is ``ssac_act_run``: the observation is
@@ -21,7 +21,20 @@ list starts with ssac_act_ingest_f32, which moves the frames out of the host-wri
 ``rolling=False`` for an encoder whose forward_rolling / reset_rolling are the pass-through inherited from ``Encoder`` (this
 package's or the reference's; no shipped encoder overrides them): the plan is not keyed on it, both share one noise stream.
 
-What stays on the general path (agent.py's eager code, unchanged): encoders that override their rolling interface (they keep
+MLP-encoder agents (``--shared_encoder`` of the reference's gym / dmc / d4rl scripts, its visgrid encoder, nets.MlpEncoder: what
+mlp_encoder.find_mlp_encoder recognises -- on the first acting call, if no update has looked at the encoder yet, with the
+shapes of that observation and a probe that moves no global random stream): the observation under the encoder's
+``ssac_obs_key`` may have any shape with num_envs * in_features elements (visgrid hands over (18, 18)) and any dtype that
+``np.ascontiguousarray(v, np.float32)`` converts as ``_process_obs``'s ``.float()`` does -- the identity plan's rule; the plan's
+observation buffer holds float32 rows and its key is (rule, num_envs, bonus) whatever dtype the caller hands over.  The
+encoder's forward (MlpEncoderEngine.forward_ptr, in the form the engine picks for that many rows) is recorded in front of the
+rule's launches, from the observation buffer into a plan-owned (num_envs, embedding) buffer; its launches point into the
+engine's arena, so an optimizer step or an in-place load_state_dict is seen by the next call, and the encoder's first-layer
+weight pointer is part of the plan's signature, so a deep copy, a ``.to()`` or a re-packed arena drops the plan.
+``rolling=True`` follows the pixel rule.  Measured: profiles/mlp_encoder.md ("Acting").
+
+What stays on the general path (agent.py's eager code, unchanged): MLP-encoder agents the update functions refuse (bf16-marked
+networks, critic- or member-sharded agents), encoders that override their rolling interface (they keep
 state between calls) under ``rolling=True``, float32 frames unless FLOAT32_FRAMES is set, float64 and other frame dtypes, injected noise
 (a hook on ``rng.draw_normal`` -- the parity tests), ensembles above 32 members, UCB networks outside the fused kernels' shapes
 (hidden > 256), ``from_cpu=False`` callers, Beta actors (beta_dist=True), and every (agent, rule, num_envs) whose recording
@@ -50,16 +63,19 @@ _STREAM_SALT = 0x41C7A11D5EEDB00C      # the acting noise stream: the agent's en
 
 
 class _Plan:
-    def __init__(self, agent, rule, n, dev, pixel_shape=None, pixel_dtype=np.uint8):
+    def __init__(self, agent, rule, n, dev, pixel_shape=None, pixel_dtype=np.uint8, mlp_in=None):
         self.rule, self.n, self.dev = rule, n, dev
         self.S = agent.encoder.embedding_dim
         self.pixel_shape = pixel_shape    # (C, H, W) of an image observation that goes through the pixel encoder, or None
+        self.mlp_in = mlp_in              # values per row of an observation that goes through a two-layer MLP encoder, or None
         self.obs_dtype = np.dtype(np.float32 if pixel_shape is None else pixel_dtype)   # what the host writes: uint8 / float32 frames
-        self.key = agent.encoder.ssac_identity_key if pixel_shape is None else getattr(agent.encoder, "ssac_obs_key", "obs")
+        self.key = agent.encoder.ssac_identity_key if pixel_shape is None and mlp_in is None \
+            else getattr(agent.encoder, "ssac_obs_key", "obs")
         self.discrete = bool(agent.discrete)
         self.A = agent.act_space_size
         self.out_floats = n if self.discrete else n * self.A
-        obs_bytes = 4 * n * self.S if pixel_shape is None else n * int(np.prod(pixel_shape)) * self.obs_dtype.itemsize
+        obs_bytes = 4 * n * (self.S if mlp_in is None else mlp_in) if pixel_shape is None \
+            else n * int(np.prod(pixel_shape)) * self.obs_dtype.itemsize
         self.handle = lib.ssac_act_create(obs_bytes, self.out_floats)
         if not self.handle:
             raise RuntimeError("libssac_hip: " + lib.ssac_last_error().decode())
@@ -94,7 +110,9 @@ def _signature(agent, with_critics):
     sig = [a.fc1.weight.data_ptr() for a in agent.actors]
     if not lu.is_identity(agent.encoder):
         conv = _conv_module(agent)
-        sig.append(conv.conv1.weight.data_ptr() if conv is not None else 0)
+        mlp = None if conv is not None else agent.encoder.__dict__.get("_ssac_mlp_desc")
+        # (an MLP encoder's first-layer weight: a deep copy, a .to() or a re-packed arena moves it)
+        sig.append(conv.conv1.weight.data_ptr() if conv is not None else mlp[0].weight.data_ptr() if mlp else 0)
     if with_critics:
         sig += [c.nets[0].fc1.weight.data_ptr() for c in agent.critics]
     return tuple(sig)
@@ -129,6 +147,36 @@ def _pixel_obs(agent, obs, num_envs):
     return key, shape, v.dtype
 
 
+def _probe_shapes(obs, num_envs):
+    """{key: shape-only tensor with a leading batch axis} of a numpy observation, as _process_obs would batch it"""
+    return {k: torch.empty(((1,) if num_envs == 1 else ()) + tuple(v.shape), device="meta")
+            for k, v in obs.items() if isinstance(v, np.ndarray)}
+
+
+def _mlp_obs(agent, obs, num_envs):
+    """(key, values per row) when the observation feeds a two-layer MLP encoder (mlp_encoder.find_mlp_encoder: an encoder
+    nobody has looked at yet is recognised here, on its first acting call, with the shapes of this observation; the probe
+    moves no global random stream) and has num_envs rows of lin0.in_features values -- in any shape and any dtype that
+    converts to float32, the identity plan's rule -- else None.  Agents the update functions refuse with such an encoder
+    (encoder_base.refuse_unsupported: bf16-marked networks, critic- or member-sharded agents) act on the general path"""
+    from . import mlp_encoder, parallel
+    enc = agent.encoder
+    if _conv_module(agent) is not None:
+        return None
+    desc = mlp_encoder.find_mlp_encoder(enc, None if mlp_encoder.is_mlp_encoder(enc) else _probe_shapes(obs, num_envs))
+    if desc is None:
+        return None
+    lin0, key = desc[0], desc[3]
+    v = obs.get(key)
+    if not isinstance(v, np.ndarray) or v.size != num_envs * lin0.in_features:
+        return None
+    if any(o.__dict__.get("_ssac_precision") == "bf16" for o in list(agent.actors) + list(agent.critics)):
+        return None
+    if parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None:
+        return None
+    return key, lin0.in_features
+
+
 def _inherits_rolling(cls):
     """the class's rolling interface is the pass-through it inherited -- forward_rolling = forward, reset_rolling a no-op
     (nets.Encoder here; nets/__init__.py:26-30 of the reference, for adopted agents: its Encoder is found among the bases by
@@ -154,7 +202,8 @@ def _eligible(agent, obs, num_envs, sample, rolling):
         v = obs.get(agent.encoder.ssac_identity_key)
         if not isinstance(v, np.ndarray) or v.size != num_envs * agent.encoder.embedding_dim:
             return False
-    elif (rolling and not _rolling_passthrough(agent.encoder)) or _pixel_obs(agent, obs, num_envs) is None:
+    elif (rolling and not _rolling_passthrough(agent.encoder)) or \
+            (_pixel_obs(agent, obs, num_envs) is None and _mlp_obs(agent, obs, num_envs) is None):
         return False          # (an encoder that overrides its rolling interface keeps state between calls: the general path)
     E = len(agent.actors)
     if E > MAX_MEMBERS or agent.act_space_size > 64:
@@ -293,6 +342,12 @@ def _record_launches(plan, agent, which):
                 img_ptr, u8 = plan.frames.data_ptr(), 0
             plan.conv_engine.forward_ptr(img_ptr, (n,) + plan.pixel_shape, u8, plan.srep.data_ptr(), S, False)
             x_in = plan.srep.data_ptr()
+        elif plan.mlp_in is not None:
+            # the MLP encoder's forward on the float32 rows where the host wrote them, into a buffer of this plan; the hidden
+            # rows live in the engine's workspace (the plan holds the engine), the launches point into its arena
+            plan.srep = plan.buf(n, S)
+            plan.enc_engine.forward_ptr(plan.obs_dev, (n, plan.mlp_in), 0, plan.srep.data_ptr(), S, False)
+            x_in = plan.srep.data_ptr()
         if plan.rule == "forward":
             if E > 1:   # one launch over the packed actors; plan.outs[e] are views of its output
                 pa = _Pack(plan, arenas)
@@ -383,19 +438,26 @@ def _record_launches(plan, agent, which):
     plan.lists[which] = idx
 
 
-def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
-    """the fast path's answer -- (action as numpy, dist_out or None) -- or None when the call is not eligible"""
-    if not _eligible(agent, obs, num_envs, sample, rolling):
-        return None
-    dev = next(agent.actors[0].parameters()).device
+def _plan_key(agent, obs, num_envs, sample):
+    """(rule, ucb, the key of the call's plan in _PLANS[agent])"""
     ucb = bool(sample and agent.ucb_bonus > 0)
     rule = ("ducb" if agent.discrete else "ucb") if ucb else ("sample" if sample else "forward")
     # (the discrete UCB rule is keyed as the sample rule it replaces, told apart by its bonus)
     # (... and never by `rolling`: a pass-through rolling call is the same call.  float32 frames of a pixel agent: a plan of
     #  their own beside the uint8 one)
     pkey = ("sample" if rule == "ducb" else rule, num_envs, float(agent.ucb_bonus) if ucb else 0.0)
-    if not lu.is_identity(agent.encoder) and obs[agent.encoder.ssac_obs_key].dtype == np.float32:
-        pkey += ("float32",)
+    if not lu.is_identity(agent.encoder) and _conv_module(agent) is not None \
+            and obs[agent.encoder.ssac_obs_key].dtype == np.float32:
+        pkey += ("float32",)  # (frames only: an MLP encoder's plan holds float32 rows whatever dtype the caller hands over)
+    return rule, ucb, pkey
+
+
+def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
+    """the fast path's answer -- (action as numpy, dist_out or None) -- or None when the call is not eligible"""
+    if not _eligible(agent, obs, num_envs, sample, rolling):
+        return None
+    dev = next(agent.actors[0].parameters()).device
+    rule, ucb, pkey = _plan_key(agent, obs, num_envs, sample)
     failed = _FAILED.get(agent)
     if failed and pkey in failed:
         return None
@@ -406,17 +468,25 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
         if not _arena_ok(agent, dev, ucb, sample):
             return None
         pix = None if lu.is_identity(agent.encoder) else _pixel_obs(agent, obs, num_envs)
+        mlp = None if lu.is_identity(agent.encoder) or pix is not None else _mlp_obs(agent, obs, num_envs)
         eng = None
         if pix is not None:
             from . import conv_encoder
             eng = conv_encoder.conv_engine(agent.encoder, dev)   # (the module's own engine: its parameters live in its arena)
             if eng is None:
                 return None
+        elif mlp is not None:
+            from . import encoder_base
+            eng = encoder_base.encoder_engine(agent.encoder, dev)   # (recognised by _eligible: the one lookup finds its engine)
+            if eng is None:
+                return None
         plans = _PLANS.setdefault(agent, {})
         if len(plans) > 12:
             plans.clear()
-        plan = plans[pkey] = _Plan(agent, rule, num_envs, dev, *(() if pix is None else pix[1:]))
-        plan.conv_engine = eng
+        plan = plans[pkey] = _Plan(agent, rule, num_envs, dev, *(() if pix is None else pix[1:]),
+                                   mlp_in=None if mlp is None else mlp[1])
+        plan.conv_engine = eng if pix is not None else None
+        plan.enc_engine = eng if mlp is not None else None
         plan.sig = _signature(agent, ucb)   # (binding the arenas may have re-pointed the parameters)
     # the reference's host draws, in its order: random.choice(act_dists) under UCB (for the logged distribution),
     # random.choice(self.actors) otherwise (agent.py:262, 301)

@@ -8,12 +8,16 @@ probing it once on a few random rows (the precedent is ``adopt.probe_identity``)
 ``encoder_base.EncoderEngine`` like the convolution engine, so the update functions only look the engine up
 (``encoder_base.encoder_engine``).
 
-Two forms, switched by ``USE_FUSED`` (the tests' A/B, not user configuration):
+Three forms, switched by ``USE_FUSED`` and ``USE_ROWS`` (the tests' A/B, not user configuration):
     per layer   ssac_linear_fwd twice + ssac_enc_act_fwd; ssac_enc_act_bwd, ssac_linear_dgrad_masked and the split-K
                 weight-gradient launches (every shape)
     fused       ssac_enc_mlp2_fwd / ssac_enc_mlp2_bwd: both layers in one launch each, the hidden tile kept in LDS,
                 followed by the same weight-gradient launches.  The default only where it measured faster
                 (ssac_enc_mlp2_supported: the forward at K <= 32); the fused backward runs under USE_FUSED = "all" only
+    rows        ssac_enc_mlp2_fwd_rows: the forward of 1 .. 16 rows that keeps nothing for a backward (an acting call, a
+                module's own forward): no MFMA tile, layer 1 spread over H / 4 workgroups, layer 2 by the last of them to
+                arrive.  The default only where ssac_enc_mlp2_rows_supported says it measured faster; USE_ROWS = "all"
+                runs it wherever it is covered.  Never taken with save=True: the update paths keep their forms
 """
 import torch
 from torch import nn
@@ -26,6 +30,10 @@ from .encoder_base import EncoderEngine, arena_layout, cached_engine  # noqa: F4
 # (profiles/mlp_encoder.md); False: every layer on its own launches; "all": both fused launches, forward AND backward,
 # wherever the shape is covered -- the fused backward measured faster at no shape, so only this setting runs it
 USE_FUSED = True
+# True: ssac_enc_mlp2_fwd_rows for save=False forwards where ssac_enc_mlp2_rows_supported says it measured faster than the
+# form the call would take otherwise (profiles/mlp_encoder.md, "Acting"); False: never; "all": wherever it is covered
+USE_ROWS = True
+ROWS_SCRATCH = 4 + 16 * 256   # SSAC_ENC_ROWS_SCRATCH: the arrival counter and the hidden rows of the few-row forward
 WGRAD_SLICES = 8         # split-K slices of a weight-gradient product, at most
 WGRAD_MIN_ROWS = 64      # rows per slice, at least
 
@@ -153,6 +161,12 @@ class MlpEncoderEngine(EncoderEngine):
             return bool(lib.ssac_enc_mlp2_covered(M, self.K, self.H, self.emb))
         return bool(USE_FUSED and lib.ssac_enc_mlp2_supported(M, self.K, self.H, self.emb))
 
+    def rows(self, M):
+        """the forward of an M-row batch that saves nothing takes the few-row launch"""
+        if USE_ROWS == "all":
+            return bool(lib.ssac_enc_mlp2_rows_covered(M, self.K, self.H, self.emb))
+        return bool(USE_ROWS and lib.ssac_enc_mlp2_rows_supported(M, self.K, self.H, self.emb))
+
     def fused_backward(self, M):
         return USE_FUSED == "all" and bool(lib.ssac_enc_mlp2_covered(M, self.K, self.H, self.emb))
 
@@ -182,6 +196,13 @@ class MlpEncoderEngine(EncoderEngine):
         ldx = self.K if ldx is None else int(ldx)
         st = engine.stream()
         K, H, N = self.K, self.H, self.emb
+        if not save and self.rows(B):
+            # (the scratch block is zeroed once, when the workspace makes it; every launch leaves its counter at zero)
+            scratch = self.ws.get("t.rows", (ROWS_SCRATCH,), zero=True)
+            check(lib.ssac_enc_mlp2_fwd_rows(x_ptr, ldx, self.lin0.weight.data_ptr(), self.lin0.bias.data_ptr(),
+                                             self.lin1.weight.data_ptr(), self.lin1.bias.data_ptr(), B, K, H, N, self.act2,
+                                             dst_ptr, ld_dst, scratch.data_ptr(), st))
+            return
         hs = self.ws.get("s.h" if save else "t.h", (B, H))
         fused = self.fused(B)
         if fused:

@@ -6,16 +6,25 @@
   2. one eager critic_update at the SAC shape (obs 17, A 6, hidden 256, 2 critics, B 256) with a SharedEncoder-shaped
      encoder beside the same call with an identity encoder: the fixed cost the encoder adds.
 
+  3. acting (--acting): the three forward forms at 1 and 4 rows (per layer, the fused tile launch, the few-row launch
+     ssac_enc_mlp2_fwd_rows), and the wall time per environment step of agent.sample_action / agent.forward with the
+     recorded plan (acting.ENABLED) on and off, for a SharedEncoder-shaped SAC agent (obs 17, A 6, hidden 256) and a
+     visgrid-shaped discrete agent, beside the identity-encoder plan at the same actor shape (the floor).  --steps-only
+     skips the launches (the part a checkout without the few-row launch can run: its "off" row is that commit's path).
+
 Method: device events around windows of REPS back-to-back launches after a warm-up, ROUNDS windows per form with the forms
 alternating inside every round; reported per launch: median over the rounds and their min .. max (the spread a difference
 has to exceed).  Clocks are whatever the device runs at under this load (not pinned); nothing else is measured in the
 same process.
 
-    python tools/measure_mlp_encoder.py [out.txt]
+Steps: wall-clock windows of 200 calls with the result consumed, otherwise the same scheme.
+
+    python tools/measure_mlp_encoder.py [out.txt] [--acting [--steps-only]]
 """
 import copy
 import os
 import sys
+import time
 from itertools import chain
 
 import numpy as np
@@ -142,9 +151,119 @@ def critic(out):
     out("   " + fmt(compare(calls, reps=50)))
 
 
+def wall_window(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    return (time.perf_counter() - t0) * 1e6 / reps   # us per call
+
+
+def compare_wall(forms, reps=REPS):
+    for fn in forms.values():
+        for _ in range(WARM):
+            fn()
+    got = {k: [] for k in forms}
+    for _ in range(ROUNDS):
+        for k, fn in forms.items():
+            got[k].append(wall_window(fn, reps))
+    return {k: (float(np.median(v)), min(v), max(v)) for k, v in got.items()}
+
+
+def acting_launches(out):
+    """the three forward forms on a few rows, as a plan would record them (no H_save)"""
+    from super_sac_amd import engine
+    from super_sac_amd._lib import check, lib
+    st = engine.stream()
+    for K, H, N, act in SHAPES:
+        for B in (1, 4):
+            g = torch.Generator().manual_seed(1)
+            dev = lambda *s: torch.randn(*s, generator=g).cuda()
+            X, W0, b0, W1, b1 = dev(B, K), dev(H, K) / K ** 0.5, dev(H), dev(N, H) / H ** 0.5, dev(N)
+            Hs, Y = torch.empty(B, H, device="cuda"), torch.empty(B, N, device="cuda")
+            scratch = torch.zeros(4 + 16 * 256, device="cuda")
+            a = ACT[act]
+
+            def fused():
+                check(lib.ssac_enc_mlp2_fwd(X.data_ptr(), K, W0.data_ptr(), b0.data_ptr(), W1.data_ptr(), b1.data_ptr(), B, K,
+                                            H, N, a, 0, Y.data_ptr(), N, st))
+
+            def layers():
+                check(lib.ssac_linear_fwd(X.data_ptr(), K, W0.data_ptr(), K, b0.data_ptr(), Hs.data_ptr(), H, B, H, K, 1, st))
+                check(lib.ssac_linear_fwd(Hs.data_ptr(), H, W1.data_ptr(), H, b1.data_ptr(), Y.data_ptr(), N, B, N, H,
+                                          1 if a == 1 else 0, st))
+                if a == 2:
+                    check(lib.ssac_enc_act_fwd(Y.data_ptr(), N, B, N, a, st))
+
+            def rows():
+                check(lib.ssac_enc_mlp2_fwd_rows(X.data_ptr(), K, W0.data_ptr(), b0.data_ptr(), W1.data_ptr(), b1.data_ptr(), B,
+                                                 K, H, N, a, Y.data_ptr(), N, scratch.data_ptr(), st))
+            out(f"{K}->{H}->{N} {act} rows {B}")
+            out("   forward : " + fmt(compare({"fused": fused, "per-layer": layers, "few-row": rows})))
+
+
+def acting_steps(out):
+    import super_sac_amd as ssa
+    import mlp_encoder_cases as mc
+    from super_sac_amd import acting
+    from super_sac_amd import mlp_encoder as me
+    dev = torch.device("cuda")
+    has_rows = hasattr(me, "USE_ROWS")
+
+    def agent(enc, A, discrete):
+        ag = ssa.Agent(act_space_size=A, encoder=enc, discrete=discrete, ensemble_size=1, num_critics=2, hidden_size=256,
+                       actor_network_cls=ssa.nets.DiscreteActor if discrete else ssa.nets.ContinuousStochasticActor,
+                       critic_network_cls=ssa.nets.DiscreteCritic if discrete else ssa.nets.ContinuousCritic,
+                       auto_rescale_targets=False)
+        ag.to(dev)
+        return ag
+    kinds = [("SharedEncoder-shaped SAC agent (obs 17 -> 128 -> 17 relu, A 6, hidden 256)", (17,), 6, False,
+              lambda: mc.SharedEncoderLike(17, 128), lambda: ssa.nets.IdentityEncoder(17)),
+             ("visgrid-shaped discrete agent (18 x 18 -> 256 -> 2 tanh, A 4, hidden 256)", (18, 18), 4, True,
+              lambda: mc.VisgridEncoderLike(18, 256, 2), lambda: ssa.nets.IdentityEncoder(2))]
+    for title, shape, A, discrete, make_enc, make_id in kinds:
+        for n in (1, 4):
+            rs = np.random.RandomState(n)
+            obs = rs.standard_normal(shape if n == 1 else (n,) + shape).astype(np.float32)
+            emb = 17 if not discrete else 2
+            flat = rs.standard_normal((emb,) if n == 1 else (n, emb)).astype(np.float32)
+            torch.manual_seed(0)
+            plain, forced, ident = agent(make_enc(), A, discrete), agent(make_enc(), A, discrete), agent(make_id(), A, discrete)
+
+            def general(fn):
+                def call():
+                    acting.ENABLED = False
+                    try:
+                        return fn()
+                    finally:
+                        acting.ENABLED = True
+                return call
+
+            def with_rows(fn):
+                def call():   # (the form is settled when the plan is recorded: the switch matters in the first call only)
+                    saved = me.USE_ROWS
+                    me.USE_ROWS = "all"
+                    try:
+                        return fn()
+                    finally:
+                        me.USE_ROWS = saved
+                return call
+            for rule in ("sample_action", "forward"):
+                forms = {"plan": lambda: getattr(plain, rule)({"obs": obs}, num_envs=n),
+                         "off": general(lambda: getattr(plain, rule)({"obs": obs}, num_envs=n)),
+                         "identity plan": lambda: getattr(ident, rule)({"obs": flat}, num_envs=n)}
+                if has_rows:
+                    forms["plan, few-row"] = with_rows(lambda: getattr(forced, rule)({"obs": obs}, num_envs=n))
+                res = compare_wall(forms)
+                taken = (rule.split("_")[0], n, 0.0) in (acting._PLANS.get(plain) or {})
+                out(f"{title}, num_envs {n}, {rule} (plan taken: {taken})")
+                out("   " + fmt(res))
+
+
 def main():
     assert torch.cuda.is_available(), "this measurement needs the GPU"
-    path = sys.argv[1] if len(sys.argv) > 1 else None
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    path = args[0] if args else None
     lines = []
 
     def out(s):
@@ -154,6 +273,11 @@ def main():
             with open(path, "w") as f:
                 f.write("\n".join(lines) + "\n")
     out(f"device: {torch.cuda.get_device_name(0)}; REPS {REPS}, ROUNDS {ROUNDS}, warm-up {WARM}")
+    if "--acting" in sys.argv:
+        if "--steps-only" not in sys.argv:
+            acting_launches(out)
+        acting_steps(out)
+        return
     kernels(out)
     critic(out)
 
