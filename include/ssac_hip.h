@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 13
+#define SSAC_ABI_VERSION 14
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -174,6 +174,13 @@ ssac_step *ssac_step_create(void *ring, int n_slots, int slot_bytes, int n_rows,
 int ssac_step_add_list(ssac_step *step, ssac_launch_list *list);
 int ssac_step_run(ssac_step *step, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot, int64_t draw,
                   void *stream);
+/* ssac_step_run + the slot's AUX word: the int32 pad at logslot_off + 4 (ssac_step_run leaves it zero) takes aux_bits --
+ * the bits of a float that a recorded launch reads from the device mirror of the slot (ssac_feed.dst), e.g. the
+ * exploration process's scale of THIS update (ssac_explore_action's scale_ptr).  The host may run n_slots updates ahead
+ * of the device, so a per-update value has to ride in the ring.  Fails when the slot has no such word (logslot_off + 8 >
+ * slot_bytes, or the draw number starts inside it). */
+int ssac_step_run_aux(ssac_step *step, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot,
+                      int32_t aux_bits, int64_t draw, void *stream);
 /* ssac_step_run hands the address of the slot it has just written to the replayed launches BY VALUE (a pointer member of
  * their recorded argument bytes is overwritten before each re-issue), so no workgroup reads the ssac_feed block to find
  * its inputs: one dependent load from cold memory less at the front of every workgroup of the update's first launch.
@@ -553,6 +560,27 @@ int ssac_action_invariance_det_bwd(const float *out_o, int64_t ld_o, const float
  * a <- clamp(a + clamp(scale * noise, +-clip), -1 + 1e-6, 1 - 1e-6)  (clip <= 0: no noise clipping). */
 int ssac_exploration_noise(float *act, int64_t ld_act, int64_t act_col0, const float *noise, float noise_scale,
                            float noise_clip, int n_rows, int act_dim, void *stream);
+/* Head, then exploration process, in ONE launch (the next action of the TD target, learning_utils.py:329-338): per element
+ * (b, i) of the actor's head output `out` (n_rows x ld_out)
+ *   tanh_normal != 0 (out is n_rows x 2A): log_std = lo + 0.5 (hi - lo) (tanh(out[b][A + i]) + 1), sd = exp(log_std),
+ *       u = out[b][i] + sd eps[b][i], a = tanh(u), and -- logp != NULL -- logp[b] = sum_i of ssac_tanh_normal_fwd's terms
+ *       in index order (log pi of the sample BEFORE the process);
+ *   tanh_normal == 0 (out is n_rows x A; eps and logp must be NULL): a = tanh(out[b][i]);
+ *   then GaussianExplorationNoise.sample (learning_utils.py:48-59): nz = scale * noise[b][i], clamped to +-noise_clip
+ *       when noise_clip > 0, act_dst[b * ld_act + act_col0 + i] = clamp(a + nz, -1 + 1e-6, 1 - 1e-6).
+ * The same fp32 expressions in the same order as ssac_tanh_normal_fwd + ssac_exploration_noise / ssac_det_action_fwd:
+ * given the same eps, noise and scale the results are the same bits.
+ * eps, noise (n_rows x act_dim, dense): device buffers, or NULL = drawn inside the launch from the engine's Philox
+ * stream (rng must then be given): draw number d = rng->offset + *rng->counter, eps = element (b, i) of draw d under
+ * the key rng->seed (ssac_philox_normal's out[b * act_dim + i]), the process noise the same element of the same draw under
+ * the key rng->seed ^ 0xE5A1C0DE0D15EA5E -- the two fields of one update are independent and share one draw number.
+ * scale: read from *scale_ptr (device-visible memory: a recorded launch sees THIS update's scale, e.g. the aux word of
+ * ssac_step_run_aux) when scale_ptr != NULL, else the by-value `scale`.
+ * act_dim <= 256 (one workgroup holds whole rows); n_rows <= 0 returns 0 without a launch. */
+int ssac_explore_action(const float *out, int64_t ld_out, int tanh_normal, float log_std_lo, float log_std_hi,
+                        const float *eps, const float *noise, const ssac_rng *rng, const float *scale_ptr, float scale,
+                        float noise_clip, int n_rows, int act_dim, float *act_dst, int64_t ld_act, int64_t act_col0,
+                        float *logp, void *stream);
 /* log-probability of a ContinuousDeterministic action under its Normal(loc, 1e-4) (distributions.py:107-114), summed over
  * the action dimensions; eps (n_rows x act_dim, nullable): the rsample draw (NULL: the action is loc itself). */
 int ssac_det_logprob(const float *eps, int n_rows, int act_dim, float *logp, void *stream);

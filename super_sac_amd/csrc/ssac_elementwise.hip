@@ -1809,8 +1809,9 @@ extern "C" int ssac_step_seek(ssac_step *s, int64_t k) {
     return 0;
 }
 
-extern "C" int ssac_step_run(ssac_step *s, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot,
-                             int64_t draw, void *stream) {
+// aux_bits: the 4-byte word behind the log slot (logslot_off + 4; ssac_step_run leaves it zero)
+static int step_run(ssac_step *s, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot, int32_t aux_bits,
+                    int64_t draw, void *stream) {
     if (!s || !idx_host || (s->n_ids > 0 && !ids_host)) return ssac_fail("ssac_step_run: null argument");
     const int64_t k = s->k;
     const int slot = (int)(k % s->n_slots);
@@ -1825,6 +1826,7 @@ extern "C" int ssac_step_run(ssac_step *s, const int64_t *idx_host, const int32_
     memcpy(st, idx_host, 8 * (size_t)s->n_rows);
     if (s->n_ids > 0) memcpy(st + s->ids_off, ids_host, 4 * (size_t)s->n_ids);
     memcpy(st + s->logslot_off, &log_slot, 4);
+    if (s->logslot_off + 8 <= s->slot_bytes) memcpy(st + s->logslot_off + 4, &aux_bits, 4);
     if (s->draw_off >= 0) memcpy(st + s->draw_off, &draw, 8);
     memcpy(s->ring + (size_t)slot * s->slot_bytes, st, (size_t)s->slot_bytes);
     __builtin_ia32_sfence();
@@ -1838,6 +1840,20 @@ extern "C" int ssac_step_run(ssac_step *s, const int64_t *idx_host, const int32_
     }
     s->k = k + 1;
     return 0;
+}
+
+extern "C" int ssac_step_run(ssac_step *s, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot,
+                             int64_t draw, void *stream) {
+    return step_run(s, idx_host, ids_host, log_slot, 0, draw, stream);
+}
+
+// ... and the slot's aux word (the bits of a float the recorded launches read from the device mirror of the slot: the
+// exploration process's scale of THIS update, ssac_explore_action)
+extern "C" int ssac_step_run_aux(ssac_step *s, const int64_t *idx_host, const int32_t *ids_host, int32_t log_slot,
+                                 int32_t aux_bits, int64_t draw, void *stream) {
+    if (s && (s->logslot_off + 8 > s->slot_bytes || (s->draw_off >= 0 && s->draw_off < s->logslot_off + 8)))
+        return ssac_fail("ssac_step_run_aux: the slot has no free word behind the log slot");
+    return step_run(s, idx_host, ids_host, log_slot, aux_bits, draw, stream);
 }
 
 // ---- late-bound Polyak (include/ssac_hip.h).  Ring tail: int64 begun | int64 decided | uint32 last_served | pad |

@@ -49,6 +49,7 @@ class CaptureCtx:
         self.published = False    # set once a captured launch has published the log block
         self.tick_ptr = 0         # device address of the update counter (ssac_feed.tick), for in-kernel noise
         self.noise_offset = 0     # draw number of this agent's noise stream at capture time
+        self.scale_ptr = 0        # device address of the float an exploration process's scale is read from (slot aux word)
         self.collective = None    # callable(fn): ends the open recording, runs fn() now, opens the next segment
         self.deferred = None      # ssac_deferred_logs of this recorded update (deferred log finalisation), or None
         self.deferred_chain = False  # the chained launch was issued with the finishing workgroup

@@ -11,6 +11,7 @@ import collections
 import ctypes as C
 import operator
 import os
+import struct
 import types
 
 import numpy as np
@@ -156,7 +157,8 @@ class _SlotLayout(collections.namedtuple(
         [B int64 replay indices | n_pad int32 subset ids | int32 log-ring slot, int32 pad | int64 noise draw number]
     n_pad = n_sub rounded up to 8 bytes; ids_off, logslot_off, draw_off = where the last three start; nbytes = the slot
     rounded up to whole 16-byte words (ssac_feed contract); slot_words, logslot_word = nbytes and logslot_off in the
-    4-byte words ssac_feed counts in.  The ONE place that knows it: the staging and device views, ssac_feed, the capture's
+    4-byte words ssac_feed counts in; aux_off = the pad word, which carries the bits of one float per update (the
+    exploration process's scale, ssac_step_run_aux; zero otherwise).  The ONE place that knows it: the staging and device views, ssac_feed, the capture's
     draw-number address and ssac_step_create all read these fields (tests/test_critic_recording_cpu.py holds them to
     ssac_step_create's geometry check)."""
     __slots__ = ()
@@ -167,9 +169,13 @@ class _SlotLayout(collections.namedtuple(
         nbytes = (logslot_off + 16 + 15) // 16 * 16
         return super().__new__(cls, B, n_sub, n_pad, 8 * B, logslot_off, logslot_off + 8, nbytes, nbytes // 4, logslot_off // 4)
 
+    @property
+    def aux_off(self):
+        return self.logslot_off + 4
+
     def host_views(self, stage):
-        """of a (slots, nbytes) uint8 numpy array: indices (slots, B) int64, [ids..., log slot at [n_pad], pad]
-        (slots, n_pad + 2) int32, draw number (slots, 1) int64"""
+        """of a (slots, nbytes) uint8 numpy array: indices (slots, B) int64, [ids..., log slot at [n_pad], aux word at
+        [n_pad + 1]] (slots, n_pad + 2) int32, draw number (slots, 1) int64"""
         return (stage[:, :self.ids_off].view(np.int64), stage[:, self.ids_off:self.draw_off].view(np.int32),
                 stage[:, self.draw_off:self.draw_off + 8].view(np.int64))
 
@@ -191,13 +197,16 @@ class _FeedRing:
 
 class _RecordedCritic:
     """one recorded critic update of an agent (agent.__dict__["_ssac_graphs"][key]), every field it ever holds.
-    The call: refs pins the objects whose ids are in the key (buffer, target agent, critic optimizer, log_alpha).
+    The call: refs pins the objects whose ids are in the key (buffer, target agent, critic optimizer, log_alpha, the
+    exploration process or None).
     The inputs, made once by prepare() (feed is None before) -- what follows from the call and the agent: dev, log_ring
     (the device's LogRing), shard and n_critics (the GLOBAL ensemble); and the fixed addresses: layout (_SlotLayout); inbuf, the device block
     the first launch pulls a slot into, with its views idx_dev / ids_dev; stage, the host copy of the ring the slots are
     composed in, with np_idx / np_i32 / np_draw; ring (_FeedRing); feed (the ssac_feed struct on the device); eps_dev
-    (injected noise, stochastic actors; else None); logblk (the log block the launches write); late_word (late-bound
-    Polyak decision word, or None).
+    (injected noise, stochastic actors; else None); proc_dev (injected noise of the exploration process, continuous
+    agents called with one; else None: the call carries no process the update looks at); scale_ptr (device address of
+    the slot mirror's aux word, where ssac_explore_action reads the process's scale of the update; 0 without proc_dev);
+    logblk (the log block the launches write); late_word (late-bound Polyak decision word, or None).
     What a recording produced, dropped by drop_recording() (graph is None: nothing recorded): graph (_LaunchList or
     CUDAGraph), dicts (the replay dicts handed back), members (the MemberUpdate records a replay reads), log_index
     ({log key: word of logblk}), log_views ({ring slot: {log key: 0-dim view}}), in_kernel_noise (the noise source it was
@@ -209,7 +218,7 @@ class _RecordedCritic:
     update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path)."""
     __slots__ = ("refs", "dev", "log_ring", "shard", "n_critics",
                  "layout", "inbuf", "idx_dev", "ids_dev", "stage", "np_idx", "np_i32", "np_draw", "ring", "feed", "eps_dev",
-                 "logblk", "late_word",
+                 "proc_dev", "scale_ptr", "logblk", "late_word",
                  "graph", "dicts", "members", "log_index", "log_views", "in_kernel_noise", "deferred", "late_arenas",
                  "td_stats", "fast",
                  "calls", "k", "path", "pending", "events")
@@ -221,7 +230,7 @@ class _RecordedCritic:
         self.members, self.log_views, self.in_kernel_noise = [], {}, False
         self.calls, self.k, self.path = 0, 0, "slow"
 
-    def prepare(self, agent, B, n_sub):
+    def prepare(self, agent, B, n_sub, explore=False):
         """One fixed device block holds the per-update inputs (_SlotLayout).  The host writes them into slot k % FEED_SLOTS
         of the input ring; the first recorded launch pulls the slot in (ssac_feed in include/ssac_hip.h), so an update is
         ONE graph launch and no copy node."""
@@ -242,6 +251,9 @@ class _RecordedCritic:
         self.events = [None] * (FEED_SLOTS // EVENT_EVERY)
         actor = agent.actors[0]
         self.eps_dev = (torch.empty(B, actor.action_size, device=dev) if lu.actor_kind(actor) == "stochastic" else None)
+        # an exploration process inside the update (TD3 / DDPG / AWAC): its noise, and where its scale arrives
+        self.proc_dev = torch.empty(B, actor.action_size, device=dev) if explore else None
+        self.scale_ptr = self.inbuf.data_ptr() + lay.aux_off if explore else 0
         self.logblk = torch.zeros(lu.LOG_WIDTH, device=dev)
         # late-bound Polyak (include/ssac_hip.h): the decision word the update's first launch writes
         self.late_word = torch.zeros(4, dtype=torch.int32, device=dev) if lu.LATE_POLYAK else None
@@ -297,7 +309,7 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     graphable = (USE_GRAPHS and engine.CAPTURE is None and agent.ensemble_size == 1 and not per and not is_beta
                  and parallel.member_shard_of(agent) is None
                  and not update_priorities and not dr3_coeff and lu.is_identity(agent.encoder)
-                 and random_process is None and torch.cuda.is_available()
+                 and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE) and torch.cuda.is_available()
                  # critic-sharded ranks: recorded launch lists only (the collective sits between two segments),
                  # continuous actions on the fused kernels (empty subset slots, in-launch TD target)
                  and (shard is None or (LAUNCH_MODE == "list" and SHARDED_LISTS and not discrete
@@ -306,11 +318,13 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     if not graphable:
         return _critic_update_eager(**kw)
     key = (id(buffer), id(target_agent), id(critic_optimizer), batch_size, float(gamma), critic_clip,
-           target_critic_ensemble_n, bool(pop), bool(discrete), id(log_alphas[0]), engine.USE_FUSED)
+           target_critic_ensemble_n, bool(pop), bool(discrete), id(log_alphas[0]), engine.USE_FUSED,
+           id(random_process), noise_clip)   # (noise_clip is baked into the recorded argument bytes)
     cache = agent.__dict__.setdefault("_ssac_graphs", {})  # lives and dies with the agent
     gs = cache.get(key)
     if gs is None:
-        gs = cache[key] = _RecordedCritic((buffer, target_agent, critic_optimizer, log_alphas[0]))  # the key's ids, pinned
+        # the key's ids, pinned
+        gs = cache[key] = _RecordedCritic((buffer, target_agent, critic_optimizer, log_alphas[0], random_process))
     gs.calls += 1
     if gs.calls <= GRAPH_WARMUP or len(buffer) < batch_size:
         return _critic_update_eager(**kw)
@@ -342,6 +356,8 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
     idx_cpu = rng.draw_indices(len(buffer), lay.B)
     if gs.eps_dev is not None and not in_kernel_noise:
         rng.draw_normal_into(gs.eps_dev)  # injected noise (parity tests) goes straight into the update's input buffer
+    if gs.proc_dev is not None and not in_kernel_noise:
+        rng.draw_normal_into(gs.proc_dev)  # ... and behind the head's, the exploration process's (learning_utils.py:331-335)
     ids = rng.draw_subset(gs.n_critics, lay.n_sub)
     slot_i = gs.log_ring.advance()
     if gs.shard is not None and gs.k % EVENT_EVERY == 0:
@@ -352,6 +368,25 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
         draw = ns[1]
         ns[1] += 1
     return idx_cpu, ids, slot_i, draw
+
+
+def _in_kernel_noise(gs, agent):
+    """does a recording of gs draw its action noise inside its launches (the agent's Philox stream)?  The fused
+    actor-sample launch does (wide action heads take the per-layer path), and so does the head-only launch of an update
+    with an exploration process (ssac_explore_action), whatever the actor's arena looks like."""
+    if not (lu.IN_KERNEL_NOISE and rng.normal_is_stock()):
+        return False
+    actor = agent.actors[0]
+    return gs.proc_dev is not None or (lu.actor_kind(actor) == "stochastic"
+                                       and engine.bind_arena(actor, "self", [actor], gs.dev).fused)
+
+
+def _scale_bits(gs, kw):
+    """the slot's aux word of the update about to be issued: the process's scale NOW (the acting loop anneals it), as
+    the int32 with the float's bits; 0 for a recording without a process"""
+    if gs.proc_dev is None:
+        return 0
+    return struct.unpack("<i", struct.pack("<f", float(kw["random_process"].current_scale)))[0]
 
 
 def _close_update(gs, agent, idx_cpu, ids, slot_i):
@@ -417,7 +452,7 @@ class _FastStep:
         gs = self.gs
         if gs.fast is not self or LAUNCH_MODE != "list" or len(self.buffer) < self.B:
             return False
-        if gs.eps_dev is not None and rng.normal_is_stock() != self.in_kernel_noise:
+        if (gs.eps_dev is not None or gs.proc_dev is not None) and rng.normal_is_stock() != self.in_kernel_noise:
             return False  # a noise hook was installed / removed: the slow path records the update again
         self.calls += 1
         if self.calls & 255 == 0:
@@ -443,7 +478,11 @@ class _FastStep:
             _flush_other_recordings(agent, keep=gs)
         idx_cpu, ids, slot_i, draw = _host_inputs(gs, self.buffer, agent, self.in_kernel_noise)
         _slot_codes(self.ids_c, ids, gs.shard)
-        check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, draw, engine.stream()))
+        if gs.proc_dev is None:
+            check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, draw, engine.stream()))
+        else:
+            check(lib.ssac_step_run_aux(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, _scale_bits(gs, self.kw), draw,
+                                        engine.stream()))
         if self.late_arenas is not None:
             agent.critics[0].__dict__["_ssac_last_step"] = self   # a soft_update that follows needs no launch
         return _close_update(gs, agent, idx_cpu, ids, slot_i)
@@ -464,16 +503,14 @@ def _critic_update_graphed(gs, kw):
         torch.cuda.synchronize()
         gs.path = "slow"
     if gs.feed is None:
-        gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"])
-    actor = agent.actors[0]
-    # (the in-kernel stream is used by the fused actor-sample launch only: wide action heads take the per-layer path)
-    in_kernel_noise = (lu.actor_kind(actor) == "stochastic" and lu.IN_KERNEL_NOISE and rng.normal_is_stock()
-                       and engine.bind_arena(actor, "self", [actor], gs.dev).fused)
+        gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"],
+                   explore=kw["random_process"] is not None and not kw["discrete"])
+    in_kernel_noise = _in_kernel_noise(gs, agent)
     if gs.graph is not None and gs.in_kernel_noise != in_kernel_noise:
         gs.drop_recording()
     _flush_other_recordings(agent, keep=gs if gs.graph is not None else None)
     idx_cpu, ids, slot_i, draw = _host_inputs(gs, buffer, agent, in_kernel_noise)
-    _write_slot(gs, idx_cpu, ids, slot_i, draw)
+    _write_slot(gs, idx_cpu, ids, slot_i, draw, _scale_bits(gs, kw))
     if gs.graph is None:
         _record(gs, kw, idx_cpu, ids, in_kernel_noise)   # (the launches run now AND are recorded)
     else:
@@ -485,8 +522,8 @@ def _critic_update_graphed(gs, kw):
     return out
 
 
-def _write_slot(gs, idx_cpu, ids, slot_i, draw):
-    """the Python replayer's half of ssac_step_run, before the launches: update gs.k's inputs into its slot of the ring"""
+def _write_slot(gs, idx_cpu, ids, slot_i, draw, aux=0):
+    """the Python replayer's half of ssac_step_run(_aux), before the launches: update gs.k's inputs into its slot of the ring"""
     k = gs.k
     # slot reuse: the replay that read this slot FEED_SLOTS updates ago must have finished.  One event per group of
     # EVENT_EVERY updates (recorded after the group's last update; an event costs a barrier packet on the queue).  No
@@ -499,6 +536,7 @@ def _write_slot(gs, idx_cpu, ids, slot_i, draw):
     row = gs.np_i32[s]
     _slot_codes(row, ids, gs.shard)
     row[gs.layout.n_pad] = slot_i
+    row[gs.layout.n_pad + 1] = aux
     gs.np_draw[s, 0] = draw
     check(lib.ssac_feed_write(gs.ring.ptr + s * nbytes, gs.stage.ctypes.data + s * nbytes, nbytes))
 
@@ -518,9 +556,11 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
     buffer, agent, B, dev = kw["buffer"], kw["agent"], kw["batch_size"], gs.dev
     kind = lu.actor_kind(agent.actors[0])
     gs.in_kernel_noise = in_kernel_noise
+    # (the injected noise buffers in the reference's draw order: the head's eps, then the process's noise)
     ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev,
-                            [gs.eps_dev] if (gs.eps_dev is not None and not in_kernel_noise) else [],
+                            [] if in_kernel_noise else [b_ for b_ in (gs.eps_dev, gs.proc_dev) if b_ is not None],
                             gs.logblk, feed=gs.feed.ptr)
+    ctx.scale_ptr = gs.scale_ptr
     if in_kernel_noise:
         ctx.tick_ptr = gs.inbuf.data_ptr() + gs.layout.draw_off
         ctx.noise_offset = 0
@@ -626,6 +666,9 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     logs = c.logs = {}
     st = c.st = engine.stream()
     c.train_enc = not lu.is_identity(agent.encoder)
+    # head + exploration process as one launch (recorded updates, and eager ones on the agent's Philox stream)
+    c.explore = (random_process is not None and not discrete
+                 and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE))
     # Two passes over the ensemble members, as the reference's single backward at the end implies (learning.py:45-130):
     # every member's batch, TD target and backup weights are computed BEFORE any critic is updated -- the "softmax"
     # weights of member i look at the ONLINE critics of ALL members (learning_utils.py:383-393).
@@ -752,7 +795,7 @@ def _member_targets(m, c):
     m.td, _ = lu.compute_td_targets(
         logs=c.logs, replay_dict=rd, agent=agent, target_agent=c.target_agent, ensemble_idx=m.i, log_alphas=c.log_alphas,
         ensemble_n=c.target_critic_ensemble_n, pop=c.pop, gamma=c.gamma, random_process=c.random_process,
-        noise_clip=c.noise_clip, discrete=c.discrete, _slot=c.slot, _member=m, _log_idx=m.ig)
+        noise_clip=c.noise_clip, discrete=c.discrete, _slot=c.slot, _member=m, _log_idx=m.ig, _explore=c.explore)
     lu.ensure_gathered(rd.get("_ssac"))  # (no-op when the merged launch took the gather)
     c.all_rd.append(rd)
     if c.sm_table is not None:

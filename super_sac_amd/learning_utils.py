@@ -121,6 +121,30 @@ def noise_stream(agent, device):
     return ns
 
 
+def explore_recordable(kind, has_process, discrete, identity_encoder, ensemble_size, per, sharded, launch_mode):
+    """May a critic update called with this exploration process be recorded -- as far as the PROCESS is concerned (the
+    other clauses of learning.critic_update's gate hold with or without one)?  Pure: tests/test_explore_recording_cpu.py
+    walks it over a grid.  No process, or a discrete agent (whose update never looks at it, learning_utils.py:322-328):
+    nothing to decide.  Otherwise the head + process run as ONE recorded launch (ssac_explore_action) that exists for the
+    library's launch lists, tanh-normal and deterministic heads, an identity encoder, one ensemble member, uniform
+    sampling and an unsharded agent; everything else keeps the eager path.  `sharded`: a critic or member shard.
+    The same answer decides whether an EAGER update of such an agent draws its noise from the agent's Philox stream
+    (stock generator): the warm-up calls and the recorded ones then follow one stream."""
+    if not has_process or discrete or kind == "discrete":
+        return True
+    return (launch_mode == "list" and kind in ("stochastic", "deterministic") and identity_encoder
+            and ensemble_size == 1 and not per and not sharded)
+
+
+def process_recordable(agent, random_process, discrete, per, launch_mode):
+    """explore_recordable of a critic_update call"""
+    from . import parallel
+    return explore_recordable(actor_kind(agent.actors[0]), random_process is not None, bool(discrete),
+                              is_identity(agent.encoder), agent.ensemble_size, bool(per),
+                              parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
+                              launch_mode)
+
+
 def draw_subset(num_critics, k):
     if engine.CAPTURE is not None:
         return list(engine.CAPTURE.ids)
@@ -566,8 +590,10 @@ def _upload_ids(ws, ids, device, tag):
 
 
 def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ensemble_n, log_alphas,
-                       pop, gamma, random_process, noise_clip, discrete=False, _slot=None, _member=None, _log_idx=None):
-    """learning_utils.py:298-354.  ``_member`` (critic_update only): the member's MemberUpdate record.  Its requests let
+                       pop, gamma, random_process, noise_clip, discrete=False, _slot=None, _member=None, _log_idx=None,
+                       _explore=False):
+    """learning_utils.py:298-354.  ``_explore`` (critic_update only): the call's process passes explore_recordable, so
+    head + process may run as ssac_explore_action.  ``_member`` (critic_update only): the member's MemberUpdate record.  Its requests let
     launches here take over the online critics' forward (ssac_actor_sample_critic_fwd) and the TD-independent half of their
     backward pass (ssac_target_fwd_critic_bwdu), and leave the final elementwise step with its three log values to the
     critic launch (``td_spec``; continuous actions, no PopArt); its outcomes say which of them did."""
@@ -611,6 +637,12 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     bt = replay_dict.get("_ssac")
     logp = ws.get(f"td.logp{i}", (B,))
     use_entropy = 0
+    # head + exploration process in ONE launch: every recorded update with a process, and -- one noise stream per run --
+    # the eager calls of the same agents while the noise comes from the engine's Philox stream (stock generator).  With a
+    # noise hook installed the eager calls keep the two-kernel sequences below: the parity tests hold the two against
+    # each other.
+    explore_launch = (_explore and random_process is not None and kind in ("stochastic", "deterministic")
+                      and (engine.CAPTURE is not None or (IN_KERNEL_NOISE and rng.normal_is_stock())))
     if kind == "discrete":
         ids = draw_subset(N, ensemble_n)
         sq = _subset_q(ws, shard, t_arena, ids, s1_rep, _row_stride(s1_rep), B, dev, f"td.c{i}")
@@ -635,6 +667,8 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
                                                  float(random_process.current_scale),
                                                  float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
                 use_entropy = 0
+        elif explore_launch:
+            _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st)
         elif kind == "stochastic":
             if fuse_sample and IN_KERNEL_NOISE and rng.normal_is_stock():
                 # the noise comes from the agent's Philox stream inside the launch: draw number = host count (eager)
@@ -705,6 +739,33 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     if kind == "discrete":
         a_s1 = aout[0]  # logits; the reference returns probs here, only used by dr3
     return td, (s1_rep, a_s1)
+
+
+def _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st):
+    """a' = process(head(aout)) into the [s'|a'] buffer in one launch (ssac_explore_action; the process replaces the
+    entropy term, learning_utils.py:331-335, so log pi is written but not used).  Noise: the agent's Philox stream -- draw
+    number = host count (eager) or the slot's draw number (recorded) -- under the stock generator; inside a recording made
+    under a noise hook, the record's fixed-address buffers (head eps first, then the process noise: the reference's draw
+    order).  Scale: by value (eager), or read by the launch from the slot's aux word (recorded)."""
+    cap = engine.CAPTURE
+    tanh_normal = kind == "stochastic"
+    rs, eps_ptr, noise_ptr = None, 0, 0
+    if IN_KERNEL_NOISE and rng.normal_is_stock():
+        ns = noise_stream(agent, dev)
+        rs = _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset) if cap is not None else _lib.Rng(ns[0], 0, ns[1])
+        if cap is None:
+            ns[1] += 1
+    else:
+        assert cap is not None, "eager updates under a noise hook keep the two-kernel sequence"
+        if tanh_normal:
+            eps_ptr = draw_normal((B, A), dev).data_ptr()
+        noise_ptr = draw_normal((B, A), dev).data_ptr()
+    check(lib.ssac_explore_action(
+        aout.data_ptr(), 2 * A if tanh_normal else A, int(tanh_normal),
+        float(actor.log_std_low) if tanh_normal else 0.0, float(actor.log_std_high) if tanh_normal else 0.0,
+        eps_ptr, noise_ptr, C.addressof(rs) if rs is not None else 0, cap.scale_ptr if cap is not None else 0,
+        float(random_process.current_scale), float(noise_clip) if noise_clip is not None else 0.0, B, A,
+        x1.data_ptr(), S + A, S, logp.data_ptr() if tanh_normal else 0, st))
 
 
 def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, st, m, replay_dict,
