@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 14
+#define SSAC_ABI_VERSION 15
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -581,6 +581,27 @@ int ssac_explore_action(const float *out, int64_t ld_out, int tanh_normal, float
                         const float *eps, const float *noise, const ssac_rng *rng, const float *scale_ptr, float scale,
                         float noise_clip, int n_rows, int act_dim, float *act_dst, int64_t ld_act, int64_t act_col0,
                         float *logp, void *stream);
+/* The stacked batch of the advantage estimator (adv_estimator.py:58-79) in ONE launch (csrc/ssac_adv.hip).  X, dense,
+ * (1 + n_samples) * n_rows rows of state_dim + act_dim floats (S, A below):
+ *   X[k * n_rows + b][0:S]  = s[b * ld_s + 0:S]                      k = 0 .. n_samples
+ *   X[b][S:S+A]             = act[b * ld_act + 0:A]                  (block 0: the data action)
+ *   X[k * n_rows + b][S+i]  = candidate k of row b, k = 1 .. n_samples:
+ *       tanh_normal != 0 (out is n_rows x 2A): log_std = lo + 0.5 (hi - lo) (tanh(out[b][A + i]) + 1),
+ *           tanh(out[b][i] + exp(log_std) * eps_k[b][i]);
+ *       tanh_normal == 0 (out is n_rows x A; eps must be NULL): tanh(out[b][i]) -- no draw, n_samples equal candidates.
+ * The same fp32 expressions in the same order as ssac_tanh_normal_fwd / ssac_det_action_fwd: given the same eps the
+ * action columns are the bits those launches write, one per sample, into the same blocks.
+ * eps: a device buffer (n_samples * n_rows x act_dim, dense, sample-major: eps_k[b][i] = eps[((k-1) n_rows + b) A + i]),
+ * or NULL = drawn inside the launch from the engine's Philox stream (rng must then be given), as ssac_explore_action
+ * does it: draw number d = rng->offset + *rng->counter, key rng->seed ^ 0xADC0FFEE5A3B1E57 (a site constant of its own:
+ * the candidates share the draw number of their update's TD-target noise -- keys rng->seed and rng->seed ^
+ * 0xE5A1C0DE0D15EA5E -- and are independent of it), eps_k[b][i] = element ((k-1) n_rows + b, i) of that draw, i.e.
+ * ssac_philox_normal(out, n_samples * n_rows, act_dim)'s out[((k-1) n_rows + b) act_dim + i].
+ * State rows travel as 16-byte units where ld_s, S, S + A and the addresses of s and X are multiples of four floats,
+ * float by float otherwise.  act_dim <= 256; n_rows <= 0 returns 0 without a launch. */
+int ssac_adv_candidates(const float *s, int64_t ld_s, const float *act, int64_t ld_act, const float *out, int64_t ld_out,
+                        int tanh_normal, float log_std_lo, float log_std_hi, const float *eps, const ssac_rng *rng,
+                        int n_rows, int state_dim, int act_dim, int n_samples, float *X, void *stream);
 /* log-probability of a ContinuousDeterministic action under its Normal(loc, 1e-4) (distributions.py:107-114), summed over
  * the action dimensions; eps (n_rows x act_dim, nullable): the rsample draw (NULL: the action is loc itself). */
 int ssac_det_logprob(const float *eps, int n_rows, int act_dim, float *logp, void *stream);

@@ -167,6 +167,7 @@ SIGNATURES = {
     "ssac_action_invariance_discrete_bwd": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P],
     "ssac_exploration_noise": [_P, _L, _L, _P, _F, _F, _I, _I, _P],
     "ssac_explore_action": [_P, _L, _I, _F, _F, _P, _P, _P, _P, _F, _F, _I, _I, _P, _L, _L, _P, _P],
+    "ssac_adv_candidates": [_P, _L, _P, _L, _P, _L, _I, _F, _F, _P, _P, _I, _I, _I, _I, _P, _P],
     "ssac_det_logprob": [_P, _I, _I, _P, _P],
     "ssac_markov_logs": [_P, _F, _P, _P, _F, _F, _F, _P, _P],
     "ssac_actor_loss_bwd": [_P, _I, _I, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P],
@@ -317,7 +318,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def _load():

@@ -50,6 +50,7 @@ class CaptureCtx:
         self.tick_ptr = 0         # device address of the update counter (ssac_feed.tick), for in-kernel noise
         self.noise_offset = 0     # draw number of this agent's noise stream at capture time
         self.scale_ptr = 0        # device address of the float an exploration process's scale is read from (slot aux word)
+        self.cand = None          # injected noise of a priority refresh's candidates ((N_SAMPLES * B, A)); None: in-kernel / none
         self.collective = None    # callable(fn): ends the open recording, runs fn() now, opens the next segment
         self.deferred = None      # ssac_deferred_logs of this recorded update (deferred log finalisation), or None
         self.deferred_chain = False  # the chained launch was issued with the finishing workgroup
@@ -132,8 +133,13 @@ class Workspace:
     def __init__(self, device):
         self.device = device
         self._bufs = {}
+        # (suffix, names) while a critic update is being recorded with deferred log finalisation: the tensors those names
+        # stand for belong to THAT recording (learning._record); None otherwise
+        self.scope = None
 
     def get(self, name, shape, dtype=torch.float32, zero=False):
+        if self.scope is not None and name in self.scope[1]:
+            name += self.scope[0]
         key = (name, tuple(shape), dtype)
         buf = self._bufs.get(key)
         if buf is None:

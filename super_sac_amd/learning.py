@@ -17,7 +17,7 @@ import types
 import numpy as np
 import torch
 
-from . import beta, encoder_base, engine, parallel, rng
+from . import adv_estimator, beta, encoder_base, engine, parallel, rng
 from . import learning_utils as lu
 from . import _lib
 from ._lib import check, lib
@@ -206,6 +206,10 @@ class _RecordedCritic:
     (injected noise, stochastic actors; else None); proc_dev (injected noise of the exploration process, continuous
     agents called with one; else None: the call carries no process the update looks at); scale_ptr (device address of
     the slot mirror's aux word, where ssac_explore_action reads the process's scale of the update; 0 without proc_dev);
+    refresh (the call refreshes the replay priorities: update_priorities=True), cand_dev (injected noise of the advantage
+    estimator's candidates, (N_SAMPLES * B, A) sample-major: a refresh on a tanh-normal policy; else None), fill (the
+    buffers _host_inputs refills per update under injected noise, (before, after) the subset draw:
+    lu.recording_noise_buffers);
     logblk (the log block the launches write); late_word (late-bound Polyak decision word, or None).
     What a recording produced, dropped by drop_recording() (graph is None: nothing recorded): graph (_LaunchList or
     CUDAGraph), dicts (the replay dicts handed back), members (the MemberUpdate records a replay reads), log_index
@@ -218,7 +222,7 @@ class _RecordedCritic:
     update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path)."""
     __slots__ = ("refs", "dev", "log_ring", "shard", "n_critics",
                  "layout", "inbuf", "idx_dev", "ids_dev", "stage", "np_idx", "np_i32", "np_draw", "ring", "feed", "eps_dev",
-                 "proc_dev", "scale_ptr", "logblk", "late_word",
+                 "proc_dev", "scale_ptr", "refresh", "cand_dev", "fill", "logblk", "late_word",
                  "graph", "dicts", "members", "log_index", "log_views", "in_kernel_noise", "deferred", "late_arenas",
                  "td_stats", "fast",
                  "calls", "k", "path", "pending", "events")
@@ -230,7 +234,7 @@ class _RecordedCritic:
         self.members, self.log_views, self.in_kernel_noise = [], {}, False
         self.calls, self.k, self.path = 0, 0, "slow"
 
-    def prepare(self, agent, B, n_sub, explore=False):
+    def prepare(self, agent, B, n_sub, explore=False, refresh=False):
         """One fixed device block holds the per-update inputs (_SlotLayout).  The host writes them into slot k % FEED_SLOTS
         of the input ring; the first recorded launch pulls the slot in (ssac_feed in include/ssac_hip.h), so an update is
         ONE graph launch and no copy node."""
@@ -254,6 +258,17 @@ class _RecordedCritic:
         # an exploration process inside the update (TD3 / DDPG / AWAC): its noise, and where its scale arrives
         self.proc_dev = torch.empty(B, actor.action_size, device=dev) if explore else None
         self.scale_ptr = self.inbuf.data_ptr() + lay.aux_off if explore else 0
+        # a priority refresh inside the update (AWAC / AFBC): the candidates' noise, one block of B rows per sample
+        kind = lu.actor_kind(actor)
+        self.refresh = bool(refresh)
+        n_cand = adv_estimator.N_SAMPLES
+        self.cand_dev = (torch.empty(n_cand * B, actor.action_size, device=dev)
+                         if refresh and kind == "stochastic" else None)
+        named = {"eps": self.eps_dev, "proc": self.proc_dev}
+        if self.cand_dev is not None:
+            named.update({f"cand{k}": self.cand_dev[k * B:(k + 1) * B] for k in range(n_cand)})
+        self.fill = tuple([named[n_] for n_ in names]
+                          for names in lu.recording_noise_buffers(kind, explore, refresh, False))
         self.logblk = torch.zeros(lu.LOG_WIDTH, device=dev)
         # late-bound Polyak (include/ssac_hip.h): the decision word the update's first launch writes
         self.late_word = torch.zeros(4, dtype=torch.int32, device=dev) if lu.LATE_POLYAK else None
@@ -308,7 +323,9 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
         beta.refuse("critic_update on a critic- or member-sharded agent")
     graphable = (USE_GRAPHS and engine.CAPTURE is None and agent.ensemble_size == 1 and not per and not is_beta
                  and parallel.member_shard_of(agent) is None
-                 and not update_priorities and not dr3_coeff and lu.is_identity(agent.encoder)
+                 # a priority refresh (AWAC / AFBC) is recorded when it runs as launches on the device trees
+                 and (not update_priorities or lu.refresh_recordable(agent, buffer, per, dr3_coeff, LAUNCH_MODE))
+                 and not dr3_coeff and lu.is_identity(agent.encoder)
                  and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE) and torch.cuda.is_available()
                  # critic-sharded ranks: recorded launch lists only (the collective sits between two segments),
                  # continuous actions on the fused kernels (empty subset slots, in-launch TD target)
@@ -319,7 +336,8 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
         return _critic_update_eager(**kw)
     key = (id(buffer), id(target_agent), id(critic_optimizer), batch_size, float(gamma), critic_clip,
            target_critic_ensemble_n, bool(pop), bool(discrete), id(log_alphas[0]), engine.USE_FUSED,
-           id(random_process), noise_clip)   # (noise_clip is baked into the recorded argument bytes)
+           id(random_process), noise_clip,   # (noise_clip is baked into the recorded argument bytes)
+           bool(update_priorities))          # (the two call forms of an AFBC loop keep one recording each)
     cache = agent.__dict__.setdefault("_ssac_graphs", {})  # lives and dies with the agent
     gs = cache.get(key)
     if gs is None:
@@ -352,13 +370,19 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
     (indices -> (augmentation: none here) -> injected noise -> REDQ subset of the GLOBAL ensemble), the update's log-ring
     slot, a sharded rank's exchange check, the draw number of the agent's noise stream (one draw per update, as eager)"""
     lay = gs.layout
+    if gs.refresh:
+        # the recorded ssac_per_assign checks priority > 0 on the device: what the last update found is raised now
+        buffer._per._raise_pending()
     buffer.total_sample_calls += 1
     idx_cpu = rng.draw_indices(len(buffer), lay.B)
-    if gs.eps_dev is not None and not in_kernel_noise:
-        rng.draw_normal_into(gs.eps_dev)  # injected noise (parity tests) goes straight into the update's input buffer
-    if gs.proc_dev is not None and not in_kernel_noise:
-        rng.draw_normal_into(gs.proc_dev)  # ... and behind the head's, the exploration process's (learning_utils.py:331-335)
+    before, after = ((), ()) if in_kernel_noise else gs.fill
+    for buf in before:
+        # injected noise (parity tests) goes straight into the update's input buffers: the head's eps, behind it the
+        # exploration process's (learning_utils.py:331-335)
+        rng.draw_normal_into(buf)
     ids = rng.draw_subset(gs.n_critics, lay.n_sub)
+    for buf in after:
+        rng.draw_normal_into(buf)  # ... and the estimator's candidates of a priority refresh (adv_estimator.py:58-79)
     slot_i = gs.log_ring.advance()
     if gs.shard is not None and gs.k % EVENT_EVERY == 0:
         parallel.check_exchange()
@@ -395,6 +419,8 @@ def _close_update(gs, agent, idx_cpu, ids, slot_i):
     if gs.deferred is not None:
         gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
     rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
+    if gs.refresh:
+        rng.choice(range(agent.ensemble_size))  # ... and with the refresh's member pick (learning_utils.py:289)
     rd = gs.dicts[0]
     rd["priority_idxs"] = idx_cpu.numpy()
     rd["_subset"] = ids
@@ -504,7 +530,7 @@ def _critic_update_graphed(gs, kw):
         gs.path = "slow"
     if gs.feed is None:
         gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"],
-                   explore=kw["random_process"] is not None and not kw["discrete"])
+                   explore=kw["random_process"] is not None and not kw["discrete"], refresh=kw["update_priorities"])
     in_kernel_noise = _in_kernel_noise(gs, agent)
     if gs.graph is not None and gs.in_kernel_noise != in_kernel_noise:
         gs.drop_recording()
@@ -557,10 +583,10 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
     kind = lu.actor_kind(agent.actors[0])
     gs.in_kernel_noise = in_kernel_noise
     # (the injected noise buffers in the reference's draw order: the head's eps, then the process's noise)
-    ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev,
-                            [] if in_kernel_noise else [b_ for b_ in (gs.eps_dev, gs.proc_dev) if b_ is not None],
+    ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev, [] if in_kernel_noise else gs.fill[0],
                             gs.logblk, feed=gs.feed.ptr)
     ctx.scale_ptr = gs.scale_ptr
+    ctx.cand = None if in_kernel_noise else gs.cand_dev
     if in_kernel_noise:
         ctx.tick_ptr = gs.inbuf.data_ptr() + gs.layout.draw_off
         ctx.noise_offset = 0
@@ -576,6 +602,10 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
         # deferred log finalisation (csrc/ssac_critic_logs.h): the buffers the weight-gradient launch will leave
         # its partials in are workspace tensors with fixed names, so the struct can be built before the body runs
         ws_ = lu.agent_ws(agent, dev)
+        # ... and they belong to THIS recording: the next update's first launch finishes the previous block from them
+        # whether or not a flush has written it already, so an update of another call form in between (a second
+        # recording of the agent -- update_priorities on and off in turn -- or an eager call) must not write over them
+        ws_.scope = (f"@{id(gs):x}", ("cu.tdstats", "cu.c0.fparts", "cu.ss0"))
         N_ = c_arena_.n_nets
         ttot_ = (engine.bf16_tiles_total(c_arena_) if c_arena_.shadow is not None
                  else engine.wgrad_tiles_total(c_arena_))
@@ -628,6 +658,7 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
             graph.add_list(handle)
     finally:
         engine.CAPTURE = None
+        lu.agent_ws(agent, dev).scope = None
     gs.graph, gs.dicts = graph, dicts
     base = gs.logblk.data_ptr()
     gs.log_index = {k_: (v.data_ptr() - base) // 4 for k_, v in logs.items()}
@@ -739,7 +770,8 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     logs["gradients/critic_random_grad"] = slot[lu.L_CRITIC_GN]
     logs["gradients/encoder_criticloss_grad_norm"] = slot[lu.L_ENC_GN]
     if update_priorities:  # learning.py:139-140: advantage-based priorities on the LAST member's batch
-        lu.adjust_priorities(logs, members[-1].rd, agent, buffer)
+        lu.adjust_priorities(logs, members[-1].rd, agent, buffer, _member=members[-1],
+                             _recordable=lu.refresh_recordable(agent, buffer, per, dr3_coeff, LAUNCH_MODE))
     return logs, [m.rd for m in members]
 
 

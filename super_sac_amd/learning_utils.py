@@ -145,6 +145,47 @@ def process_recordable(agent, random_process, discrete, per, launch_mode):
                               launch_mode)
 
 
+def priority_recordable(kind, per_on_device, identity_encoder, ensemble_size, per, dr3, sharded, bf16, launch_mode):
+    """May a critic update called with update_priorities=True be recorded -- as far as the PRIORITY REFRESH is concerned
+    (learning.critic_update's other clauses hold with or without one)?  Pure: tests/test_priority_recording_cpu.py walks
+    it over the grid of its inputs.  The refresh is recorded as ssac_adv_candidates -> ensemble-Q forward ->
+    ssac_adv_filter -> ssac_per_assign on the device trees, which exists for the library's launch lists, a buffer with
+    its trees in HBM, an identity encoder, one ensemble member, uniform sampling, no DR3, an unsharded fp32 agent and a
+    tanh-normal, deterministic or discrete head (not Beta).  A process, PopArt or gradient clipping make no difference.
+    The same answer decides whether an EAGER update of such a call draws the candidates from the agent's Philox stream
+    (adjust_priorities): the warm-up calls and the recorded ones then follow one stream."""
+    return bool(launch_mode == "list" and kind in ("stochastic", "deterministic", "discrete") and per_on_device
+                and identity_encoder and ensemble_size == 1 and not per and not dr3 and not sharded and not bf16)
+
+
+def refresh_recordable(agent, buffer, per, dr3_coeff, launch_mode):
+    """priority_recordable of a critic_update call"""
+    from . import parallel
+    marks = [o.__dict__.get("_ssac_precision") for o in list(agent.actors) + list(agent.critics)]
+    return priority_recordable(actor_kind(agent.actors[0]), bool(getattr(buffer, "per_on_device", False)),
+                               is_identity(agent.encoder), agent.ensemble_size, bool(per), bool(dr3_coeff),
+                               parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
+                               "bf16" in marks, launch_mode)
+
+
+def recording_noise_buffers(kind, explore, refresh, in_kernel_noise):
+    """The noise buffers a recorded critic update owns and refills on the host before every replay: (names filled before
+    the REDQ subset is drawn, names filled after it), each in fill order, one rng.draw_normal_into call per name.  That is
+    the reference's order on the device generator: the head's eps, the exploration process's noise (`explore`: the call
+    carries a process the update looks at), and -- behind the subset, which is a Python-random draw -- the advantage
+    estimator's N_SAMPLES candidate draws of a priority refresh (`refresh`) on a tanh-normal policy.  Deterministic and
+    discrete heads draw no candidates.  Nothing at all while the noise is drawn inside the launches.  Pure (tests/
+    test_priority_recording_cpu.py); learning._RecordedCritic fills its buffers by this list."""
+    if in_kernel_noise:
+        return [], []
+    before = (["eps"] if kind == "stochastic" else []) + (["proc"] if explore and kind != "discrete" else [])
+    after = []
+    if refresh and kind == "stochastic":
+        from . import adv_estimator
+        after = [f"cand{k}" for k in range(adv_estimator.N_SAMPLES)]
+    return before, after
+
+
 def draw_subset(num_critics, k):
     if engine.CAPTURE is not None:
         return list(engine.CAPTURE.ids)
@@ -295,11 +336,13 @@ class MemberUpdate:
     launch that did the work: fwd_done, bwd_done; w3_snapshot (W3 as the chained launch saw it when it skipped dz2u, else
     None); chain (arguments of a PENDING chained launch, None once issued); td with td_spec (ssac_td_spec; None: evaluated
     already), td_logs (its log words), td_keep (tensors the spec points into); bw (backup weights); branch (side stream);
-    ss, grads, log_parts / log_nets / log_tiles, n_glob, logs_folded: what the clip and log launches read."""
+    ss, grads, log_parts / log_nets / log_tiles, n_glob, logs_folded: what the clip and log launches read; td_rng: the
+    ssac_rng (seed, counter address, offset) the TD target's noise was drawn with inside its launch, None when it came
+    from a buffer or the update has none -- a priority refresh in the same update draws its candidates at that number."""
     __slots__ = ("i", "ig", "arena", "tag", "rd", "B", "want_fwd", "s_rep", "X", "ldx", "h1", "h2", "q", "want_bwd", "act",
                  "ld_act", "dz2u", "dz1u", "dz2_optional", "lazy_td", "fwd_done", "bwd_done", "w3_snapshot", "chain", "td",
                  "td_spec", "td_logs", "td_keep", "bw", "branch", "ss", "grads", "log_parts", "log_nets", "log_tiles",
-                 "n_glob", "logs_folded")
+                 "n_glob", "logs_folded", "td_rng")
 
     def __init__(self, i, ig, arena):
         for f in self.__slots__:
@@ -668,7 +711,9 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
                                                  float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
                 use_entropy = 0
         elif explore_launch:
-            _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st)
+            td_rng = _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st)
+            if m is not None:
+                m.td_rng = td_rng
         elif kind == "stochastic":
             if fuse_sample and IN_KERNEL_NOISE and rng.normal_is_stock():
                 # the noise comes from the agent's Philox stream inside the launch: draw number = host count (eager)
@@ -678,6 +723,8 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
                 rs = _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset) if cap is not None else _lib.Rng(ns[0], 0, ns[1])
                 if cap is None:
                     ns[1] += 1
+                if m is not None:
+                    m.td_rng = (rs.seed, rs.counter, rs.offset)
                 _actor_sample(a_arena, s1_rep, B, 0, actor, x1, S, A, logp, C.addressof(rs), st, co_fwd,
                               replay_dict, chain=chain, rng_keep=rs)
                 eps = None
@@ -766,6 +813,7 @@ def _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process,
         eps_ptr, noise_ptr, C.addressof(rs) if rs is not None else 0, cap.scale_ptr if cap is not None else 0,
         float(random_process.current_scale), float(noise_clip) if noise_clip is not None else 0.0, B, A,
         x1.data_ptr(), S + A, S, logp.data_ptr() if tanh_normal else 0, st))
+    return (rs.seed, rs.counter, rs.offset) if rs is not None else None
 
 
 def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, st, m, replay_dict,
@@ -1206,11 +1254,29 @@ def _zeros(dev, n):
 # ------------------------------------------------------------------------------------------
 # AFBC helpers (learning_utils.py:217-240, 287-295)
 # ------------------------------------------------------------------------------------------
-def adjust_priorities(logs, replay_dict, agent, buffer):
-    """new PER priorities relu(A(s,a)) + 1e-4 from a random ensemble member (fresh policy samples)."""
+def adjust_priorities(logs, replay_dict, agent, buffer, _member=None, _recordable=False):
+    """new PER priorities relu(A(s,a)) + 1e-4 from a random ensemble member (fresh policy samples).
+    ``_member`` / ``_recordable`` (critic_update only): the update's MemberUpdate record and priority_recordable's answer
+    for the call.  A recordable refresh runs as launches only (AdvantageEstimator.evaluate(_update=...)): always inside a
+    recording, and in eager calls while the noise comes from the engine's Philox stream -- the candidates then share the
+    draw number of this update's TD-target noise (_member.td_rng), so eager and recorded calls follow one stream.  Eager
+    calls under a noise hook, or whose head noise is a host draw, keep the present draws and launches."""
     o, a = replay_dict["primary_batch"][0], replay_dict["primary_batch"][1]
+    cap = engine.CAPTURE
+    if cap is not None:
+        # recorded: learning._close_update makes the reference's random.choice per update; the rows are the indices of
+        # THIS update in the recording's input block, the priorities the estimator's fixed workspace tensor
+        assert _recordable and agent.ensemble_size == 1
+        res = agent.adv_estimator.evaluate(o, a, 0, want=("prio",), _update=(_member.td_rng, cap.cand))
+        buffer._per.assign_recorded(cap.idx_dev, res["prio"].reshape(-1), buffer._storage.size)
+        return
     member = rng.choice(range(agent.ensemble_size))
-    res = agent.adv_estimator.evaluate(o, a, member, want=("prio",))
+    kind = actor_kind(agent.actors[member])
+    if (_recordable and IN_KERNEL_NOISE and rng.normal_is_stock()
+            and (kind != "stochastic" or _member.td_rng is not None)):
+        res = agent.adv_estimator.evaluate(o, a, member, want=("prio",), _update=(_member.td_rng, None))
+    else:
+        res = agent.adv_estimator.evaluate(o, a, member, want=("prio",))
     # (the reference blocks here, .cpu() in learning_utils.py:293; with the trees in HBM the new priorities and the
     # indices they belong to never leave the device)
     new_priorities = res["prio"].reshape(-1)

@@ -258,6 +258,18 @@ class DevicePrioritySampler:
                 assert np.max(idxes) < n_filled
         self._assign(idxes, priorities, True, n_filled)
 
+    def assign_recorded(self, rows_dev, prio_dev, capacity):
+        """update_priorities as ONE launch on fixed addresses, for a recorded critic update (learning._record): rows and
+        priorities are device tensors the recording owns.  n_filled is the storage CAPACITY, not len(buffer): the
+        recorded argument bytes outlive this call and the buffer grows during an online run.  The rows are the indices the
+        very update drew from range(len(buffer)), so the reference's range assertion (replay.py:187) cannot fire for
+        them; the priority <= 0 check still reaches the pinned error word, which the recording's host side reads once per
+        update (_raise_pending)."""
+        assert rows_dev.dtype == torch.int64 and prio_dev.dtype == torch.float32 and rows_dev.numel() == prio_dev.numel()
+        check(lib.ssac_per_assign(self.sum_dev.data_ptr(), self.min_dev.data_ptr(), self.cap, rows_dev.data_ptr(),
+                                  rows_dev.numel(), prio_dev.data_ptr(), 0, self.alpha, self.max_dev.data_ptr(), 1,
+                                  int(capacity), self.err.data_ptr(), self.win.data_ptr(), engine.stream()))
+
     def sample_device(self, n_filled, batch_size):
         """(int64 indices, float64 weights) on the device; the uniforms come from numpy's global generator"""
         self._raise_pending()

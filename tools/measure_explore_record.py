@@ -120,9 +120,12 @@ def _worker(tree):
             print(json.dumps({"shape": name, "us": window(update, n_upd) * 1e6 / n_upd}), flush=True)
 
 
-def _driver(trees, out_path):
+def _driver(trees, out_path, script=None, shapes=None):
+    """script, shapes: the worker script and its shape names (tools/measure_priority_record.py drives its own workers
+    through this loop)"""
     import statistics
-    here = os.path.abspath(__file__)
+    here = os.path.abspath(script or __file__)
+    shapes = list(shapes or SHAPES)
     procs = {}
     for name, path in trees:
         procs[name] = subprocess.Popen([sys.executable, here, "--worker", "--tree", path], stdin=subprocess.PIPE,
@@ -140,7 +143,7 @@ def _driver(trees, out_path):
                 return json.loads(reply)
     result = {"rounds": ROUNDS, "min_window_s": MIN_WINDOW_S, "shapes": {}}
     try:
-        for shape in SHAPES:
+        for shape in shapes:
             info = {name: ask(name, f"setup {shape}") for name, _ in trees}
             got = {name: [] for name, _ in trees}
             for _ in range(ROUNDS):
@@ -150,7 +153,7 @@ def _driver(trees, out_path):
                 name: dict(info[name], median_us=statistics.median(v), min_us=min(v), max_us=max(v), windows_us=v)
                 for name, v in got.items()}
             for name, r in result["shapes"][shape].items():
-                print(f"{shape:5s} {name:8s} {r['median_us']:8.2f} us/update [{r['min_us']:.2f} .. {r['max_us']:.2f}]  "
+                print(f"{shape:13s} {name:8s} {r['median_us']:8.2f} us/update [{r['min_us']:.2f} .. {r['max_us']:.2f}]  "
                       f"recorded {r['recorded']}  launches/update {r['launches']}  window {r['window_updates']} updates",
                       flush=True)
             if out_path:
