@@ -9,6 +9,7 @@ logs stay on the device until somebody reads them.
 """
 import collections
 import ctypes as C
+import functools
 import operator
 import os
 import struct
@@ -1501,11 +1502,182 @@ def _step_and_log_norm(agent, adam, clip, clip_members, member_ss, norm_out, ms=
                                    norm_out.data_ptr(), engine.stream()))
 
 
+def _bc_head_bwd(head, out_ptr, ld_out, a, mask_ptr, B, A, lo, hi, scale, d_out_ptr, ld_d, log_ptr, total_ptr, st):
+    """ONE behavioural-cloning loss launch: scale * -mean(mask * log pi(a | .)) of the data action `a` under the `head`
+    ("discrete", "deterministic": Normal(tanh(out), 1e-4), distributions.py:107-114, else the tanh-normal with log-std
+    bounds lo / hi), its gradient to d_out, the unscaled loss to log_ptr and the scaled one added to total_ptr"""
+    if head == "discrete":
+        check(lib.ssac_bc_discrete_bwd(out_ptr, a.data_ptr(), a.stride(0), mask_ptr, B, A, scale, d_out_ptr, log_ptr,
+                                       total_ptr, st))
+    elif head == "deterministic":
+        check(lib.ssac_bc_det_logprob_bwd(out_ptr, ld_out, a.data_ptr(), a.stride(0), mask_ptr, B, A, scale, d_out_ptr,
+                                          ld_d, log_ptr, total_ptr, st))
+    else:
+        check(lib.ssac_bc_logprob_bwd(out_ptr, ld_out, a.data_ptr(), a.stride(0), mask_ptr, B, A, lo, hi, scale,
+                                      d_out_ptr, ld_d, log_ptr, total_ptr, st))
+
+
+def _action_invariance_bwd(head, out_o, aug_ptr, ld, a_inv, olp, B, A, lo, hi, scale, d_out_ptr, log_ptr, total_ptr, st):
+    """ONE launch of the action invariance constraint (learning_utils.py:272-285): loss and gradient at the actor's output
+    on the AUGMENTED observations (aug_ptr, leading dimension ld, as d_out's), against the action a_inv sampled at the
+    original ones with log-probability olp there -- a deterministic head's is tanh(out_o), which the kernel takes itself"""
+    if head == "discrete":
+        check(lib.ssac_action_invariance_discrete_bwd(out_o.data_ptr(), aug_ptr, a_inv.data_ptr(), B, A, scale,
+                                                      d_out_ptr, log_ptr, total_ptr, st))
+    elif head == "deterministic":
+        check(lib.ssac_action_invariance_det_bwd(out_o.data_ptr(), ld, aug_ptr, ld, B, A, scale, d_out_ptr, ld, log_ptr,
+                                                 total_ptr, st))
+    else:
+        check(lib.ssac_action_invariance_bwd(aug_ptr, ld, a_inv.data_ptr(), A, olp.data_ptr(), B, A, lo, hi, scale,
+                                             d_out_ptr, ld, log_ptr, total_ptr, st))
+
+
+_OfflinePlan = collections.namedtuple("_OfflinePlan",
+                                      "head out_cols row_blocks inv_draw masked train_enc enc_grad enc_path")
+
+
+@functools.lru_cache(maxsize=None)
+def _offline_member_plan(kind, discrete, filter_, invariance, pixel, update_encoder, A):
+    """THE decision of one member's offline actor update, made once from the call's flags (invariance: bool(actor_lambda));
+    touches no device and draws nothing.  The Beta refusals of offline_actor_update have passed.
+    head: the BC loss launch -- "discrete", "beta", "deterministic" or "tanh_normal"; out_cols: the head's columns.
+    row_blocks: 2 with the invariance constraint (the BC rows and the AUGMENTED rows as one stacked pass), else 1.
+    inv_draw: the host draw of the constraint's step (1) -- "categorical" (rng.draw_categorical), "normal"
+      (rng.draw_normal((B, A))), None (no constraint, or a deterministic head: its sample is tanh(out), no draw).
+    masked: the advantage filter's row mask weighs the BC loss.
+    train_enc: the BC warm-up (main.py:292-312) trains a pixel encoder THROUGH the BC loss, then clip + encoder_optimizer.step().
+    enc_grad: the actor's input gradient is wanted -- also for the constraint alone, which reaches the encoder through the
+      AUGMENTED observations whether or not update_encoder is set (only encoder_optimizer.step() depends on it).
+    enc_path: where that gradient goes -- "stacked" (the stacked pass's engine.backward, stepped behind the last member),
+      "single" (_encoder_step), None."""
+    head = "discrete" if discrete else kind if kind in ("beta", "deterministic") else "tanh_normal"
+    train_enc = update_encoder and pixel
+    enc_grad = train_enc or (invariance and pixel)
+    return _OfflinePlan(
+        head=head, out_cols=A if head in ("discrete", "deterministic") else 2 * A, row_blocks=2 if invariance else 1,
+        inv_draw={"discrete": "categorical", "tanh_normal": "normal"}.get(head) if invariance else None,
+        masked=filter_, train_enc=train_enc, enc_grad=enc_grad,
+        enc_path="stacked" if (enc_grad and invariance) else "single" if train_enc else None)
+
+
+class _OfflineMember:
+    """ONE ensemble member's offline actor update: i, actor and a_arena, plan (_offline_member_plan), lo / hi (log-std
+    bounds of a tanh-normal head), rd (replay dict), mask (the advantage filter's rows, None: all); of the invariance
+    constraint's step (1): out_o (the actor at the original observations), a_inv and olp (the action sampled there and
+    its log-probability) and eps (the draw, kept alive to the end of the member's launches); s_rep (the actor's B or 2B
+    input rows) with its row stride lds, and eng (the encoder engine behind a stacked pixel pass)"""
+    __slots__ = ("i", "actor", "a_arena", "plan", "lo", "hi", "rd", "mask", "out_o", "a_inv", "olp", "eps", "s_rep", "lds",
+                 "eng")
+
+
+def _offline_inputs(m, c):
+    """the member's replay dict, the advantage filter's mask (the estimator draws its candidates here), the arena"""
+    if c.premade_replay_dicts is not None:
+        m.rd = c.premade_replay_dicts[m.i]
+    else:
+        m.rd = lu.sample_move_and_augment(buffer=c.buffer, batch_size=c.batch_size, augmenter=c.augmenter,
+                                          aug_mix=c.aug_mix, per=c.per, _invariance=m.plan.row_blocks == 2)
+    m.mask = None
+    if m.plan.masked:
+        o, a = m.rd["primary_batch"][0], m.rd["primary_batch"][1]
+        m.mask = c.agent.adv_estimator.evaluate(o, a, m.i, want=("mask",), log_ptr=c.log + 4 * lu.L_ADVW)["mask"]
+        c.logs["losses/adv_weights_mean"] = c.slot[lu.L_ADVW]
+    m.a_arena = engine.bind_arena(m.actor, "self", [m.actor], c.dev)
+
+
+def _offline_invariance_sample(m, c):
+    """action invariance (learning_utils.py:272-285), step (1): at the ORIGINAL observations, without gradient, sample an
+    action from the actor's distribution and keep its log-probability there"""
+    if m.rd.get("augmented_obs") is None:
+        raise NotImplementedError("actor_lambda needs replay dicts made with the invariance observations")
+    ws, i, B, A, enc = c.ws, m.i, c.batch_size, m.actor.action_size, c.agent.encoder
+    os_rep = lu.encode(enc, m.rd["original_obs"][0], dst=ws.get("bc.osrep", (B, enc.embedding_dim)) if c.pixel else None)
+    _, _, m.out_o = engine.mlp_forward(m.a_arena, os_rep, lu._row_stride(os_rep), 0, B, ws, f"bc.o{i}", save=False)
+    m.olp = ws.get(f"bc.olp{i}", (B,))
+    m.a_inv = m.eps = None   # a deterministic head's o_dist.sample() is tanh(out_o): no draw
+    if m.plan.inv_draw == "categorical":
+        m.a_inv = ws.get(f"bc.ainv{i}", (B,))
+        m.a_inv.copy_(rng.draw_categorical(m.out_o[0]))   # o_dist.sample() (device generator, as the reference)
+    elif m.plan.inv_draw == "normal":
+        m.a_inv = ws.get(f"bc.ainv{i}", (B, A))
+        m.eps = rng.draw_normal((B, A), c.dev)
+        check(lib.ssac_tanh_normal_fwd(m.out_o.data_ptr(), 2 * A, m.eps.data_ptr(), B, A, m.lo, m.hi, m.a_inv.data_ptr(), A,
+                                       0, m.olp.data_ptr(), c.st))
+
+
+def _offline_representation(m, c):
+    """the rows the actor runs on.  With the invariance constraint the BC rows and the AUGMENTED rows go through the
+    encoder / actor as ONE stacked 2B-row pass: their weight gradients add up inside one backward"""
+    enc, o, B = c.agent.encoder, m.rd["primary_batch"][0], c.batch_size
+    m.eng = None
+    if m.plan.row_blocks == 1:
+        m.s_rep = lu.encode(enc, o, save=m.plan.train_enc)
+    elif c.pixel:
+        m.eng, m.s_rep = lu.encode_stacked(enc, o, m.rd["augmented_obs"][0], c.ws, "bc.img2", c.dev)
+    else:
+        s_rep, as_rep = lu.encode(enc, o), lu.encode(enc, m.rd["augmented_obs"][0])
+        m.s_rep = c.ws.get("bc.x2", (2 * B, s_rep.shape[1]))
+        m.s_rep[:B].copy_(s_rep)
+        m.s_rep[B:].copy_(as_rep)
+    m.lds = lu._row_stride(m.s_rep)
+
+
+def _offline_loss_head(m, c):
+    """the actor on the member's rows, the BC loss head on rows [0, B), the invariance constraint on rows [B, 2B)
+    -> (h1, h2 of the forward, dL/d(output))"""
+    ws, st, slot, i, plan, B, A = c.ws, c.st, c.slot, m.i, m.plan, c.batch_size, m.actor.action_size
+    a, rows, O, total_ptr = m.rd["primary_batch"][1], plan.row_blocks * B, plan.out_cols, c.log + 4 * lu.L_BC_TOTAL
+    ah1, ah2, aout = engine.mlp_forward(m.a_arena, m.s_rep, m.lds, 0, rows, ws, f"bc.a{i}")
+    d_out = ws.get(f"bc.dout{i}", (1, rows, O))
+    if plan.head == "beta":
+        # plain behavioural cloning, loss_i = -mean(log pi(a_data|s)) (learning_utils.py:241-269, filter_=False) with
+        # x = (clamp(a, +-0.99) + 1) / 2; the two loss logs are reduced from log pi on the device
+        xg, lpg = ws.get(f"bc.xb{i}", (B, A)), ws.get(f"bc.lpb{i}", (B,))
+        beta.given_logp(aout, B, A, a, lpg, xg)
+        check(lib.ssac_beta_bwd(0, 0, 0, 0, 0, aout.data_ptr(), 2 * A, xg.data_ptr(), B, A, 0, 0, -c.inv_e, 1,
+                                d_out.data_ptr(), 2 * A, st))
+        loss_i = lpg.mean().neg()
+        slot[lu.L_BC0 + i].copy_(loss_i)
+        slot[lu.L_BC_TOTAL].add_(loss_i * c.inv_e)
+    else:
+        _bc_head_bwd(plan.head, aout.data_ptr(), O, a, engine._ptr(m.mask), B, A, m.lo, m.hi, c.inv_e, d_out.data_ptr(), O,
+                     c.log + 4 * (lu.L_BC0 + i), total_ptr, st)
+    if plan.row_blocks == 2:
+        _action_invariance_bwd(plan.head, m.out_o, aout[0, B:].data_ptr(), O, m.a_inv, m.olp, B, A, m.lo, m.hi,
+                               float(c.actor_lambda) * c.inv_e, d_out[0, B:].data_ptr(), c.log + 4 * lu.L_ACT_INV,
+                               total_ptr, st)
+    return ah1, ah2, d_out
+
+
+def _offline_backward(m, c, ah1, ah2, d_out):
+    """the actor's backward and the encoder's share of it (ensemble members share the encoder: member i > 0 adds its
+    gradient, the clip / step follows the last member)  -> the member's sum-of-squares slots"""
+    ws, i, plan, B, S, last = c.ws, m.i, m.plan, c.batch_size, m.s_rep.shape[1], m.i == c.E - 1
+    dX, ss = _actor_backward(m.a_arena, d_out, m.s_rep, m.lds, ah1, ah2, plan.row_blocks * B, ws, "bc", i, c.adam,
+                             c.actor_clip, c.clip_members, need_dx=plan.enc_grad)
+    if plan.enc_path == "stacked":
+        # the BC rows carry a gradient only when the encoder is trained through the BC loss (filtered_bc_loss computes
+        # s_rep without gradient otherwise), the augmented rows always do; the encoder is clipped and logged either
+        # way and stepped only with update_encoder (learning.py:203-208)
+        d_rep = ws.get("bc.drep2", (2 * B, S))
+        d_rep.copy_(dX[0])
+        if not plan.train_enc:
+            d_rep[:B].zero_()
+        m.eng.backward(d_rep, accumulate=i > 0)
+        if last:
+            m.eng.optimizer_step(c.encoder_optimizer, c.encoder_clip, norm_out=c.slot[lu.L_ENC_GN:], step=plan.train_enc)
+    elif plan.enc_path == "single":  # (dX was taken before the epilogue of the weight-gradient launch touched W1)
+        _encoder_step(c.agent.encoder, c.encoder_optimizer, c.encoder_clip, dX, S, ws, c.slot, c.dev, accumulate=i > 0,
+                      step=last)
+    return ss
+
+
 def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batch_size, actor_clip,
                          update_encoder, encoder_clip, augmenter, actor_lambda, aug_mix,
                          premade_replay_dicts=None, per=True, discrete=False, filter_=True):
     """learning.py:144-219: advantage-filtered behavioural cloning (AWAC / AFBC actor update), optionally on a
-    prioritised batch whose priorities are refreshed from the advantage afterwards."""
+    prioritised batch whose priorities are refreshed from the advantage afterwards.  What a member's update consists of
+    is decided in ONE place, _offline_member_plan; the steps below read that answer."""
     engine.require_gpu()
     lu.ensure_adopted(agent, buffer)
     encoder_base.refuse_unsupported(agent, "offline_actor_update", actor_lambda=actor_lambda)
@@ -1514,140 +1686,38 @@ def offline_actor_update(buffer, agent, actor_optimizer, encoder_optimizer, batc
             beta.refuse("offline_actor_update with the advantage filter (filter_=True)")
         if actor_lambda:
             beta.refuse("offline_actor_update with the action invariance constraint (actor_lambda)")
-    E = agent.ensemble_size
-    # the BC warm-up (main.py:292-312) trains a pixel encoder THROUGH the BC loss: the actor's input gradient goes
-    # back through the conv engine, then clip + encoder_optimizer.step()
-    pixel = not lu.is_identity(agent.encoder)
-    train_enc = bool(update_encoder) and pixel
-    # the action invariance constraint (learning_utils.py:272-285) reaches the encoder through the AUGMENTED
-    # observations whether or not update_encoder is set (only encoder_optimizer.step() depends on it)
-    enc_grad = train_enc or (bool(actor_lambda) and pixel)
-    # (ensemble members share the encoder: member i > 0 adds its gradient, the clip / step follows the last member)
-    dev = next(agent.actors[0].parameters()).device
-    ws = lu.agent_ws(agent, dev)
-    adam = engine.adam_group(actor_optimizer, dev)
-    slot = lu.log_block(dev, adam)
-    logs = {}
-    st = engine.stream()
-    inv_e = 1.0 / E
-    clip_members, member_ss = [], []
-    rd = None
+    c = types.SimpleNamespace(**locals())   # the call: its arguments, and below what every member shares
+    E = c.E = agent.ensemble_size
+    pixel = c.pixel = not lu.is_identity(agent.encoder)
+    dev = c.dev = next(agent.actors[0].parameters()).device
+    c.ws = lu.agent_ws(agent, dev)
+    adam = c.adam = engine.adam_group(actor_optimizer, dev)
+    slot = c.slot = lu.log_block(dev, adam)
+    c.log = slot.data_ptr()   # (word k of the fp32 log block: c.log + 4 * k, the address slot[k:] has)
+    logs = c.logs = {}
+    c.st = engine.stream()
+    c.inv_e = 1.0 / E
+    c.clip_members, member_ss = [], []
     for i in range(E):
-        if premade_replay_dicts is not None:
-            rd = premade_replay_dicts[i]
-        else:
-            rd = lu.sample_move_and_augment(buffer=buffer, batch_size=batch_size, augmenter=augmenter,
-                                            aug_mix=aug_mix, per=per, _invariance=bool(actor_lambda))
-        o, a = rd["primary_batch"][0], rd["primary_batch"][1]
-        actor = agent.actors[i]
-        mask_ptr = 0
-        if filter_:
-            res = agent.adv_estimator.evaluate(o, a, i, want=("mask",), log_ptr=slot[lu.L_ADVW:].data_ptr())
-            mask_ptr = res["mask"].data_ptr()
-            logs["losses/adv_weights_mean"] = slot[lu.L_ADVW]
-        a_arena = engine.bind_arena(actor, "self", [actor], dev)
-        A = actor.action_size
-        det = not discrete and lu.actor_kind(actor) == "deterministic"   # Normal(tanh(out), 1e-4), distributions.py:107-114
-        O = A if (discrete or det) else 2 * A
-        rows = batch_size
-        if actor_lambda:
-            # ---- action invariance (learning_utils.py:272-285).  (1) at the ORIGINAL observations, without gradient:
-            #      sample an action from the actor's distribution and keep its log-probability there
-            if rd.get("augmented_obs") is None:
-                raise NotImplementedError("actor_lambda needs replay dicts made with the invariance observations")
-            oo, ao = rd["original_obs"][0], rd["augmented_obs"][0]
-            B = batch_size
-            os_rep = lu.encode(agent.encoder, oo, dst=ws.get("bc.osrep", (B, agent.encoder.embedding_dim))
-                               if pixel else None)
-            _, _, out_o = engine.mlp_forward(a_arena, os_rep, lu._row_stride(os_rep), 0, B, ws, f"bc.o{i}", save=False)
-            olp = ws.get(f"bc.olp{i}", (B,))
-            if discrete:
-                a_inv = ws.get(f"bc.ainv{i}", (B,))
-                a_inv.copy_(rng.draw_categorical(out_o[0]))   # o_dist.sample() (device generator, as the reference)
-            elif det:
-                a_inv = None   # o_dist.sample() is tanh(out_o): no draw; the constraint kernel takes out_o itself
-            else:
-                a_inv = ws.get(f"bc.ainv{i}", (B, A))
-                eps = rng.draw_normal((B, A), dev)
-                check(lib.ssac_tanh_normal_fwd(out_o.data_ptr(), 2 * A, eps.data_ptr(), B, A,
-                                               float(actor.log_std_low), float(actor.log_std_high), a_inv.data_ptr(), A,
-                                               0, olp.data_ptr(), st))
-            # (2) the BC rows and the AUGMENTED rows go through the encoder / actor as ONE stacked 2B-row pass: their
-            #     weight gradients add up inside one backward
-            if pixel:
-                eng, X2 = lu.encode_stacked(agent.encoder, o, ao, ws, "bc.img2", dev)
-            else:
-                s_rep, as_rep = lu.encode(agent.encoder, o), lu.encode(agent.encoder, ao)
-                X2 = ws.get("bc.x2", (2 * B, s_rep.shape[1]))
-                X2[:B].copy_(s_rep)
-                X2[B:].copy_(as_rep)
-            s_rep, rows = X2, 2 * B
-        else:
-            s_rep = lu.encode(agent.encoder, o, save=train_enc)
-        B, S = batch_size, s_rep.shape[1]
-        lds = lu._row_stride(s_rep)
-        ah1, ah2, aout = engine.mlp_forward(a_arena, s_rep, lds, 0, rows, ws, f"bc.a{i}")
-        d_out = ws.get(f"bc.dout{i}", (1, rows, O))
-        if discrete:
-            check(lib.ssac_bc_discrete_bwd(aout.data_ptr(), a.data_ptr(), a.stride(0), mask_ptr, B, A, inv_e,
-                                           d_out.data_ptr(), slot[lu.L_BC0 + i:].data_ptr(),
-                                           slot[lu.L_BC_TOTAL:].data_ptr(), st))
-            if actor_lambda:
-                check(lib.ssac_action_invariance_discrete_bwd(
-                    out_o.data_ptr(), aout[0, B:].data_ptr(), a_inv.data_ptr(), B, A, float(actor_lambda) * inv_e,
-                    d_out[0, B:].data_ptr(), slot[lu.L_ACT_INV:].data_ptr(), slot[lu.L_BC_TOTAL:].data_ptr(), st))
-        elif lu.actor_kind(actor) == "beta":
-            # plain behavioural cloning, loss_i = -mean(log pi(a_data|s)) (learning_utils.py:241-269, filter_=False) with
-            # x = (clamp(a, +-0.99) + 1) / 2; the two loss logs are reduced from log pi on the device
-            xg, lpg = ws.get(f"bc.xb{i}", (B, A)), ws.get(f"bc.lpb{i}", (B,))
-            beta.given_logp(aout, B, A, a, lpg, xg)
-            check(lib.ssac_beta_bwd(0, 0, 0, 0, 0, aout.data_ptr(), 2 * A, xg.data_ptr(), B, A, 0, 0, -inv_e, 1,
-                                    d_out.data_ptr(), 2 * A, st))
-            loss_i = lpg.mean().neg()
-            slot[lu.L_BC0 + i].copy_(loss_i)
-            slot[lu.L_BC_TOTAL].add_(loss_i * inv_e)
-        elif det:
-            check(lib.ssac_bc_det_logprob_bwd(aout.data_ptr(), A, a.data_ptr(), a.stride(0), mask_ptr, B, A, inv_e,
-                                              d_out.data_ptr(), A, slot[lu.L_BC0 + i:].data_ptr(),
-                                              slot[lu.L_BC_TOTAL:].data_ptr(), st))
-            if actor_lambda:
-                check(lib.ssac_action_invariance_det_bwd(
-                    out_o.data_ptr(), A, aout[0, B:].data_ptr(), A, B, A, float(actor_lambda) * inv_e,
-                    d_out[0, B:].data_ptr(), A, slot[lu.L_ACT_INV:].data_ptr(), slot[lu.L_BC_TOTAL:].data_ptr(), st))
-        else:
-            check(lib.ssac_bc_logprob_bwd(aout.data_ptr(), 2 * A, a.data_ptr(), a.stride(0), mask_ptr, B, A,
-                                          float(actor.log_std_low), float(actor.log_std_high), inv_e,
-                                          d_out.data_ptr(), 2 * A, slot[lu.L_BC0 + i:].data_ptr(),
-                                          slot[lu.L_BC_TOTAL:].data_ptr(), st))
-            if actor_lambda:
-                check(lib.ssac_action_invariance_bwd(
-                    aout[0, B:].data_ptr(), 2 * A, a_inv.data_ptr(), A, olp.data_ptr(), B, A,
-                    float(actor.log_std_low), float(actor.log_std_high), float(actor_lambda) * inv_e,
-                    d_out[0, B:].data_ptr(), 2 * A, slot[lu.L_ACT_INV:].data_ptr(), slot[lu.L_BC_TOTAL:].data_ptr(), st))
+        m = _OfflineMember()
+        m.i, actor = i, agent.actors[i]
+        m.actor = actor
+        plan = m.plan = _offline_member_plan(lu.actor_kind(actor), bool(discrete), bool(filter_), bool(actor_lambda), pixel,
+                                             bool(update_encoder), actor.action_size)
+        m.lo, m.hi = (float(actor.log_std_low), float(actor.log_std_high)) if plan.head == "tanh_normal" else (0.0, 0.0)
+        _offline_inputs(m, c)
+        if plan.row_blocks == 2:
+            _offline_invariance_sample(m, c)
+        _offline_representation(m, c)
+        ah1, ah2, d_out = _offline_loss_head(m, c)
         logs[f"losses/filterd_bc_loss_{i}"] = slot[lu.L_BC0 + i]
-        dX, ss = _actor_backward(a_arena, d_out, s_rep, lds, ah1, ah2, rows, ws, "bc", i, adam, actor_clip, clip_members,
-                                 need_dx=enc_grad)
-        if enc_grad and actor_lambda:
-            # stacked encoder pass: the BC rows carry a gradient only when the encoder is trained through the BC loss
-            # (filtered_bc_loss computes s_rep without gradient otherwise), the augmented rows always do; the encoder
-            # is clipped and logged either way and stepped only with update_encoder (learning.py:203-208)
-            d_rep = ws.get("bc.drep2", (2 * B, S))
-            d_rep.copy_(dX[0])
-            if not train_enc:
-                d_rep[:B].zero_()
-            eng.backward(d_rep, accumulate=i > 0)
-            if i == E - 1:
-                eng.optimizer_step(encoder_optimizer, encoder_clip, norm_out=slot[lu.L_ENC_GN:], step=train_enc)
-        elif train_enc:  # (dX was taken before the epilogue of the weight-gradient launch touched W1)
-            _encoder_step(agent.encoder, encoder_optimizer, encoder_clip, dX, S, ws, slot, dev, accumulate=i > 0,
-                          step=i == E - 1)
-        member_ss.append(ss)
+        member_ss.append(_offline_backward(m, c, ah1, ah2, d_out))
     logs["losses/filtered_bc_overall_loss"] = slot[lu.L_BC_TOTAL]
-    _step_and_log_norm(agent, adam, actor_clip, clip_members, member_ss, slot[lu.L_BC_GN:])
+    _step_and_log_norm(agent, adam, actor_clip, c.clip_members, member_ss, slot[lu.L_BC_GN:])
     logs["gradients/actor_offline_grad_norm"] = slot[lu.L_BC_GN]
     logs["gradients/encoder_offline_actorloss_grad_norm"] = slot[lu.L_ENC_GN]  # identity encoders: no gradient
     if per:
-        lu.adjust_priorities(logs, rd, agent, buffer)
+        lu.adjust_priorities(logs, m.rd, agent, buffer)
     return logs
 
 
@@ -1702,19 +1772,14 @@ def markov_state_abstraction_update(buffer, agent, optimizer, batch_size, augmen
     # ---- loss heads (each also leaves its share of d markov_loss / d output)
     A = inv.action_size
     if discrete:
-        d_iout = ws.get("mk.dinv", (1, B, A))
-        check(lib.ssac_bc_discrete_bwd(iout.data_ptr(), a.data_ptr(), a.stride(0), 0, B, A, float(inverse_coeff),
-                                       d_iout.data_ptr(), slot[lu.L_MK_RAW:].data_ptr(),
-                                       slot[lu.L_MK_TMP:].data_ptr(), st))
-        inv_scale = 1.0
+        head, O, lo, hi, inv_scale, coeff = "discrete", A, 0.0, 0.0, 1.0, float(inverse_coeff)
     else:
         # -a_dist.log_prob(a).mean(): the mean runs over the B x A per-dimension log-probabilities (learning.py:298)
-        d_iout = ws.get("mk.dinv", (1, B, 2 * A))
-        check(lib.ssac_bc_logprob_bwd(iout.data_ptr(), 2 * A, a.data_ptr(), a.stride(0), 0, B, A,
-                                      float(inv.log_std_low), float(inv.log_std_high), float(inverse_coeff) / A,
-                                      d_iout.data_ptr(), 2 * A, slot[lu.L_MK_RAW:].data_ptr(),
-                                      slot[lu.L_MK_TMP:].data_ptr(), st))
-        inv_scale = 1.0 / A
+        head, O, lo, hi = "tanh_normal", 2 * A, float(inv.log_std_low), float(inv.log_std_high)
+        inv_scale, coeff = 1.0 / A, float(inverse_coeff) / A
+    d_iout = ws.get("mk.dinv", (1, B, O))
+    _bc_head_bwd(head, iout.data_ptr(), O, a, 0, B, A, lo, hi, coeff, d_iout.data_ptr(), O, slot[lu.L_MK_RAW:].data_ptr(),
+                 slot[lu.L_MK_TMP:].data_ptr(), st)
     d_cout = ws.get("mk.dcon", (1, 2 * B, 1))
     check(lib.ssac_bce_sigmoid_bwd(cout.data_ptr(), B, 2 * B, float(contrastive_coeff), d_cout.data_ptr(),
                                    slot[lu.L_MK_CON:].data_ptr(), st))
