@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 15
+#define SSAC_ABI_VERSION 16
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -700,6 +700,25 @@ int ssac_softmax_weights(const float *q, int n_members, int n_rows, float temp, 
  * learning_utils.py:375, 389) and out is (n_rows), otherwise out is (n_rows x q_dim). */
 int ssac_ensemble_min_select(const float *q, int n_nets, int n_rows, int q_dim, const float *act, int64_t ld_act,
                              float *out, void *stream);
+
+/* ---- ensemble members of one recorded critic update (csrc/ssac_members.hip; ensemble_size > 1, SUNRISE).
+ * ssac_members_sunrise_weights: the SUNRISE backup weights of ALL n_members member batches in one launch.  q
+ * (n_members * n_nets nets, n_members * n_rows rows, q_dim) is ONE packed forward of every member's target critics (net
+ * k * n_nets + j = net j of member k) over the members' stacked batches (member i owns rows [i * n_rows, (i + 1) * n_rows)).
+ * w (n_members x n_rows): w[i][b] = sigmoid(-std_unbiased_k(min_j q[k * n_nets + j][i * n_rows + b][sel]) * temp) + 0.5,
+ * sel = (int)act[(i * n_rows + b) * ld_act] for q_dim > 1 (act: the STACKED batch's taken actions, required then), else 0.
+ * logs[0..3] (may be NULL) = mean, max, min, std of the LAST member's weights (the reference's member loop overwrites
+ * them).  Per element the fp32 operations of ssac_ensemble_min_select followed by ssac_sunrise_weights, in their order:
+ * the same bits as that pair on the same q.  2 <= n_members <= SSAC_MAX_MEMBERS. */
+#define SSAC_MAX_MEMBERS 8
+int ssac_members_sunrise_weights(const float *q, int n_members, int n_nets, int n_rows, int q_dim, float temp,
+                                 const float *act, int64_t ld_act, float *w, float *logs, void *stream);
+/* ssac_group_norms over ONE of n_buffers (<= SSAC_MAX_MEMBERS) equally shaped sum-of-squares buffers: sumsq is a HOST
+ * array of their device addresses (copied into the launch's arguments), *pick a device-resident int32 read by the launch
+ * (clamped to [0, n_buffers)) -- in a recorded update the aux word of the slot's device mirror, so that the recorded
+ * launches do not depend on which member learning.py:135 picked.  Summation order and clip scale as ssac_group_norms. */
+int ssac_group_norms_pick(const float *const *sumsq, int n_buffers, const int32_t *pick, int n_groups, int group_size,
+                          const ssac_adam_ctl *scale_by_clip, float *out, void *stream);
 
 /* ---- DrQ augmentations: augmentations.py:214-263 (Drqv2Aug) and :165-204 (DrqAug).
  * src: uint8 or fp32 images (n x c x h x h) gathered through idx (may be NULL = identity);

@@ -181,6 +181,8 @@ SIGNATURES = {
     "ssac_sunrise_weights": [_P, _I, _I, _F, _P, _P, _P],
     "ssac_softmax_weights": [_P, _I, _I, _F, _P, _P, _P],
     "ssac_ensemble_min_select": [_P, _I, _I, _I, _P, _L, _P, _P],
+    "ssac_members_sunrise_weights": [_P, _I, _I, _I, _I, _F, _P, _L, _P, _P, _P],
+    "ssac_group_norms_pick": [_P, _I, _P, _I, _I, _P, _P, _P],
     "ssac_drq_shift": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P],
     "ssac_aug_chain": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
     "ssac_aug_colour_jitter": [_P, _I, _P, _I, _I, _I, _I, _P, C.c_uint32, _I, _P, _P],
@@ -318,7 +320,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def _load():

@@ -60,6 +60,22 @@ class CaptureCtx:
         self.late_used = False
         self.defer_begin = False  # the replay gather will also do ssac_begin_update's work (vector buffers)
         self.pending_begin = None # (log block, adam ctl ptr) waiting for that gather
+        self.members = None       # (E, rows, ids) per member of a recorded ensemble update, or None (one member)
+        self.pick_ptr = 0         # device address of the int32 naming the member whose gradient norm is logged (slot aux word)
+
+    def set_member(self, i):
+        """a recorded ensemble update (members = (E, B, n)): the draw sites hand out member i's block of the update's
+        inputs from here on -- rows [i B, (i + 1) B) of the indices, ids [i n, (i + 1) n) of the subsets -- and its noise
+        is draw number (slot's draw word) + i of the agent's stream"""
+        if self.members is None:
+            return
+        if not hasattr(self, "_all"):
+            self._all = (self.idx_cpu, self.idx_dev, self.ids, self.ids_dev)
+        _, B, n = self.members
+        idx_cpu, idx_dev, ids, ids_dev = self._all
+        self.idx_cpu, self.idx_dev = idx_cpu[i * B:(i + 1) * B], idx_dev[i * B:(i + 1) * B]
+        self.ids, self.ids_dev = ids[i * n:(i + 1) * n], ids_dev[i * n:(i + 1) * n]
+        self.noise_offset = i
 
 
 CAPTURE = None

@@ -104,12 +104,17 @@ def _split_forward(n_nets, n_rows):
     return SPLIT_FORWARD and n_nets * ((n_rows + 31) // 32) <= 192
 
 
-def _clip_and_step(adam, members, clip, slot_norm, member_shard=None):
+def _clip_and_step(adam, members, clip, slot_norm, member_shard=None, joint_ss=None):
     """clip_grad_norm_ over ALL listed arenas jointly, then Adam from the stored gradients
     (learning.py:122-130 / :413-416).  members: list of (arena, key, grads, sumsq).  member_shard: the joint norm runs
-    over the members of EVERY rank (one SUM all-reduce of this rank's squared norm)."""
+    over the members of EVERY rank (one SUM all-reduce of this rank's squared norm).  joint_ss: the members' sumsq
+    buffers as ONE tensor they are views of, in member order (recordable ensemble updates: no concatenation between the
+    launches)."""
     st = engine.stream()
-    allss = members[0][3] if len(members) == 1 else torch.cat([m[3] for m in members])
+    if joint_ss is not None:
+        allss = joint_ss
+    else:
+        allss = members[0][3] if len(members) == 1 else torch.cat([m[3] for m in members])
     if member_shard is not None:
         allss = allss.sum().reshape(1)   # (device plumbing: one scalar to exchange)
         parallel.all_reduce_sum(allss)
@@ -220,13 +225,16 @@ class _RecordedCritic:
     Progress: fast (the _FastStep over the recording's launch lists; None: not built, retired because a parameter moved, or
     dropped with its recording), calls (critic_update calls with this key, warm-up included), k (updates issued on the ring, by either
     replayer), path ("fast": the C step issued the last one, "slow": Python did), pending (log-ring slot of the newest
-    update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path)."""
+    update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path).
+    Ensemble updates: n_members (E; 1 otherwise), eps_members (under injected noise, the E fixed (B, A) eps
+    buffers in member order; None for heads without noise), pick (the member learning.py:135 picked for the update about
+    to be issued: the slot's aux word)."""
     __slots__ = ("refs", "dev", "log_ring", "shard", "n_critics",
                  "layout", "inbuf", "idx_dev", "ids_dev", "stage", "np_idx", "np_i32", "np_draw", "ring", "feed", "eps_dev",
                  "proc_dev", "scale_ptr", "refresh", "cand_dev", "fill", "logblk", "late_word",
                  "graph", "dicts", "members", "log_index", "log_views", "in_kernel_noise", "deferred", "late_arenas",
                  "td_stats", "fast",
-                 "calls", "k", "path", "pending", "events")
+                 "calls", "k", "path", "pending", "events", "n_members", "eps_members", "pick")
 
     def __init__(self, refs):
         for f in self.__slots__:
@@ -234,11 +242,16 @@ class _RecordedCritic:
         self.refs = refs
         self.members, self.log_views, self.in_kernel_noise = [], {}, False
         self.calls, self.k, self.path = 0, 0, "slow"
+        self.n_members, self.pick = 1, 0
 
-    def prepare(self, agent, B, n_sub, explore=False, refresh=False):
+    def prepare(self, agent, B, n_sub, explore=False, refresh=False, members=1):
         """One fixed device block holds the per-update inputs (_SlotLayout).  The host writes them into slot k % FEED_SLOTS
         of the input ring; the first recorded launch pulls the slot in (ssac_feed in include/ssac_hip.h), so an update is
-        ONE graph launch and no copy node."""
+        ONE graph launch and no copy node.  members = E > 1: the layout of (E B, E n_sub) holds every member's index draw
+        and subset member-major -- B and n_sub below are the slot's."""
+        E = self.n_members = members
+        rows = B
+        B, n_sub = E * B, E * n_sub
         dev = self.dev = self.refs[3].device
         self.log_ring = lu.ring_for(dev)
         self.shard = parallel.shard_of(agent)
@@ -255,7 +268,9 @@ class _RecordedCritic:
         self.ring = _FeedRing(FEED_SLOTS * lay.nbytes)
         self.events = [None] * (FEED_SLOTS // EVENT_EVERY)
         actor = agent.actors[0]
-        self.eps_dev = (torch.empty(B, actor.action_size, device=dev) if lu.actor_kind(actor) == "stochastic" else None)
+        self.eps_dev = (torch.empty(rows, actor.action_size, device=dev) if lu.actor_kind(actor) == "stochastic" else None)
+        if E > 1 and self.eps_dev is not None:
+            self.eps_members = [self.eps_dev] + [torch.empty_like(self.eps_dev) for _ in range(E - 1)]
         # an exploration process inside the update (TD3 / DDPG / AWAC): its noise, and where its scale arrives
         self.proc_dev = torch.empty(B, actor.action_size, device=dev) if explore else None
         self.scale_ptr = self.inbuf.data_ptr() + lay.aux_off if explore else 0
@@ -304,7 +319,8 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
                   weighted_bellman_temp, weight_type, pop, augmenter, encoder_lambda, random_process,
                   noise_clip, aug_mix=0.75, discrete=False, per=False, update_priorities=False,
                   dr3_coeff=0.0):
-    """learning.py:18-141.  When the launch sequence is static (one ensemble member, vector
+    """learning.py:18-141.  When the launch sequence is static (one ensemble member -- or several under
+    learning_utils.members_recordable, DESIGN.md 7f --, vector
     observations, uniform sampling, single rank) it is captured once into a HIP graph and replayed:
     the host then only draws the indices / REDQ subset / noise, uploads them into fixed-address
     buffers and issues one graph launch, instead of ~15 kernel launches."""
@@ -322,7 +338,10 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     is_beta = lu.actor_kind(agent.actors[0]) == "beta"
     if is_beta and (shard is not None or parallel.member_shard_of(agent) is not None):
         beta.refuse("critic_update on a critic- or member-sharded agent")
-    graphable = (USE_GRAPHS and engine.CAPTURE is None and agent.ensemble_size == 1 and not per and not is_beta
+    members = agent.ensemble_size > 1 and lu.members_call_recordable(
+        agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type, weighted_bellman_temp,
+        LAUNCH_MODE)
+    graphable = (USE_GRAPHS and engine.CAPTURE is None and (agent.ensemble_size == 1 or members) and not per and not is_beta
                  and parallel.member_shard_of(agent) is None
                  # a priority refresh (AWAC / AFBC) is recorded when it runs as launches on the device trees
                  and (not update_priorities or lu.refresh_recordable(agent, buffer, per, dr3_coeff, LAUNCH_MODE))
@@ -339,6 +358,8 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
            target_critic_ensemble_n, bool(pop), bool(discrete), id(log_alphas[0]), engine.USE_FUSED,
            id(random_process), noise_clip,   # (noise_clip is baked into the recorded argument bytes)
            bool(update_priorities))          # (the two call forms of an AFBC loop keep one recording each)
+    if members:
+        key += (weight_type, weighted_bellman_temp)   # (an ensemble's backup weights are part of the recorded launches)
     cache = agent.__dict__.setdefault("_ssac_graphs", {})  # lives and dies with the agent
     gs = cache.get(key)
     if gs is None:
@@ -371,6 +392,8 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
     (indices -> (augmentation: none here) -> injected noise -> REDQ subset of the GLOBAL ensemble), the update's log-ring
     slot, a sharded rank's exchange check, the draw number of the agent's noise stream (one draw per update, as eager)"""
     lay = gs.layout
+    if gs.n_members > 1:
+        return _host_inputs_members(gs, buffer, agent, in_kernel_noise)
     if gs.refresh:
         # the recorded ssac_per_assign checks priority > 0 on the device: what the last update found is raised now
         buffer._per._raise_pending()
@@ -395,6 +418,31 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
     return idx_cpu, ids, slot_i, draw
 
 
+def _host_inputs_members(gs, buffer, agent, in_kernel_noise):
+    """_host_inputs of an ensemble update: for every member in turn its indices, its injected eps (under a noise hook),
+    its subset -- the reference's order -- into the member's block of the stacked draw; behind the last subset the member
+    whose gradient norm is logged (learning.py:135: the slot's aux word, gs.pick).  The members' TD-target noise is drawn
+    in-kernel at draw numbers d0 .. d0 + E - 1 of the agent's stream, as E eager member steps consume it."""
+    lay, E = gs.layout, gs.n_members
+    B, n = lay.B // E, lay.n_sub // E
+    idx_cpu, ids = torch.empty(lay.B, dtype=torch.int64), []
+    for i in range(E):
+        buffer.total_sample_calls += 1
+        idx_cpu[i * B:(i + 1) * B] = rng.draw_indices(len(buffer), B)
+        if not in_kernel_noise and gs.eps_members is not None:
+            rng.draw_normal_into(gs.eps_members[i])
+        ids += rng.draw_subset(gs.n_critics, n)
+    pick = rng.choice(agent.critics)
+    gs.pick = next(j for j, c_ in enumerate(agent.critics) if c_ is pick)
+    slot_i = gs.log_ring.advance()
+    draw = 0
+    if in_kernel_noise:
+        ns = lu.noise_stream(agent, gs.dev)
+        draw = ns[1]
+        ns[1] += E
+    return idx_cpu, ids, slot_i, draw
+
+
 def _in_kernel_noise(gs, agent):
     """does a recording of gs draw its action noise inside its launches (the agent's Philox stream)?  The fused
     actor-sample launch does (wide action heads take the per-layer path), and so does the head-only launch of an update
@@ -414,11 +462,26 @@ def _scale_bits(gs, kw):
     return struct.unpack("<i", struct.pack("<f", float(kw["random_process"].current_scale)))[0]
 
 
+def _aux_bits(gs, kw):
+    """the slot's aux word of the update about to be issued: an ensemble update carries no process (the gate), its word
+    names the member whose gradient norm is logged (gs.pick, drawn by _host_inputs_members); otherwise _scale_bits"""
+    return gs.pick if gs.n_members > 1 else _scale_bits(gs, kw)
+
+
 def _close_update(gs, agent, idx_cpu, ids, slot_i):
     """the update has been issued: count it, keep the Python RNG stream in step, hand out this slot's log views"""
     gs.k += 1
     if gs.deferred is not None:
         gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
+    E = gs.n_members
+    if E > 1:
+        # (learning.py:135's pick was drawn by _host_inputs_members, before the update was issued: nothing to draw here)
+        B, n = gs.layout.B // E, gs.layout.n_sub // E
+        idx_np = idx_cpu.numpy()
+        for i, rd in enumerate(gs.dicts):
+            rd["priority_idxs"] = idx_np[i * B:(i + 1) * B]
+            rd["_subset"] = ids[i * n:(i + 1) * n]
+        return dict(gs.views(slot_i)), gs.dicts
     rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
     if gs.refresh:
         rng.choice(range(agent.ensemble_size))  # ... and with the refresh's member pick (learning_utils.py:289)
@@ -446,7 +509,7 @@ class _FastStep:
         self.gs, self.kw = gs, kw
         self.buffer, self.agent = kw["buffer"], kw["agent"]
         lay = gs.layout
-        self.B = lay.B
+        self.B = lay.B // gs.n_members
         h = lib.ssac_step_create(gs.ring.ptr, FEED_SLOTS, lay.nbytes, lay.B, lay.n_sub, lay.ids_off, lay.logslot_off,
                                  lay.draw_off, EVENT_EVERY)
         if not h:
@@ -459,11 +522,13 @@ class _FastStep:
         self.late_arenas = gs.late_arenas   # (target arena, online arena) of the late-bound Polyak
         self.calls = 0
         # a few parameter addresses checked on every call (cheap), all of them every 256 calls
-        actor = self.agent.actors[0]
         tgt = kw["target_agent"]
-        self.arenas = [(self.agent.critics[0].arena(gs.dev), list(self.agent.critics[0].nets)),
-                       (tgt.critics[0].arena(gs.dev), list(tgt.critics[0].nets)),
-                       (engine.bind_arena(actor, "self", [actor], gs.dev), [actor])]
+        self.arenas = []
+        for i in range(gs.n_members):   # (every member's arenas: an ensemble update launches on all of them)
+            actor = self.agent.actors[i]
+            self.arenas += [(self.agent.critics[i].arena(gs.dev), list(self.agent.critics[i].nets)),
+                            (tgt.critics[i].arena(gs.dev), list(tgt.critics[i].nets)),
+                            (engine.bind_arena(actor, "self", [actor], gs.dev), [actor])]
         self.probes = []
         for arena, mods in self.arenas:
             lins = engine.MlpArena.linear_triples(mods[0]) + engine.MlpArena.linear_triples(mods[-1])
@@ -505,10 +570,10 @@ class _FastStep:
             _flush_other_recordings(agent, keep=gs)
         idx_cpu, ids, slot_i, draw = _host_inputs(gs, self.buffer, agent, self.in_kernel_noise)
         _slot_codes(self.ids_c, ids, gs.shard)
-        if gs.proc_dev is None:
+        if gs.proc_dev is None and gs.n_members == 1:
             check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, draw, engine.stream()))
         else:
-            check(lib.ssac_step_run_aux(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, _scale_bits(gs, self.kw), draw,
+            check(lib.ssac_step_run_aux(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, _aux_bits(gs, self.kw), draw,
                                         engine.stream()))
         if self.late_arenas is not None:
             agent.critics[0].__dict__["_ssac_last_step"] = self   # a soft_update that follows needs no launch
@@ -531,13 +596,14 @@ def _critic_update_graphed(gs, kw):
         gs.path = "slow"
     if gs.feed is None:
         gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"],
-                   explore=kw["random_process"] is not None and not kw["discrete"], refresh=kw["update_priorities"])
+                   explore=kw["random_process"] is not None and not kw["discrete"], refresh=kw["update_priorities"],
+                   members=agent.ensemble_size)
     in_kernel_noise = _in_kernel_noise(gs, agent)
     if gs.graph is not None and gs.in_kernel_noise != in_kernel_noise:
         gs.drop_recording()
     _flush_other_recordings(agent, keep=gs if gs.graph is not None else None)
     idx_cpu, ids, slot_i, draw = _host_inputs(gs, buffer, agent, in_kernel_noise)
-    _write_slot(gs, idx_cpu, ids, slot_i, draw, _scale_bits(gs, kw))
+    _write_slot(gs, idx_cpu, ids, slot_i, draw, _aux_bits(gs, kw))
     if gs.graph is None:
         _record(gs, kw, idx_cpu, ids, in_kernel_noise)   # (the launches run now AND are recorded)
     else:
@@ -584,8 +650,13 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
     kind = lu.actor_kind(agent.actors[0])
     gs.in_kernel_noise = in_kernel_noise
     # (the injected noise buffers in the reference's draw order: the head's eps, then the process's noise)
-    ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev, [] if in_kernel_noise else gs.fill[0],
+    normals = gs.fill[0] if gs.n_members == 1 else (gs.eps_members or [])   # (an ensemble's: one eps buffer per member)
+    ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev, [] if in_kernel_noise else normals,
                             gs.logblk, feed=gs.feed.ptr)
+    if gs.n_members > 1:
+        E_ = gs.n_members
+        ctx.members = (E_, gs.layout.B // E_, gs.layout.n_sub // E_)
+        ctx.pick_ptr = gs.inbuf.data_ptr() + gs.layout.aux_off
     ctx.scale_ptr = gs.scale_ptr
     ctx.cand = None if in_kernel_noise else gs.cand_dev
     if in_kernel_noise:
@@ -701,6 +772,25 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     # head + exploration process as one launch (recorded updates, and eager ones on the agent's Philox stream)
     c.explore = (random_process is not None and not discrete
                  and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE))
+    # An ensemble update that may be recorded takes ONE form in every call -- warm-up, recording, replay
+    # and USE_GRAPHS = False alike: the members' gathers write into one stacked [s | a] batch, the backup weights and the
+    # gradient-norm partials live in workspace tensors, the chained launch keeps its one-workgroup form and the picked
+    # member's gradient norm is a launch of its own.
+    c.members_form = E > 1 and ms is None and lu.members_call_recordable(
+        agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type, weighted_bellman_temp,
+        LAUNCH_MODE)
+    c.xstack = c.ss_all = None
+    c.weights_on = weight_type is not None and weighted_bellman_temp is not None
+    c.packed = False
+    if c.members_form:
+        st_ = buffer._storage
+        S_ = next(iter(st_.s_stack.values())).shape[1]
+        A_ = int(np.prod(st_.action_stack.shape[1:]))
+        c.S = S_
+        c.xstack = ws.get("cu.xstack", (E * batch_size, S_ + A_))
+        c.pack_group = (lu.members_pack_group(target_agent, E, batch_size, dev)
+                        if (c.weights_on and lu.PACKED_WEIGHTS) else 0)
+        c.packed = c.pack_group > 0
     # Two passes over the ensemble members, as the reference's single backward at the end implies (learning.py:45-130):
     # every member's batch, TD target and backup weights are computed BEFORE any critic is updated -- the "softmax"
     # weights of member i look at the ONLINE critics of ALL members (learning_utils.py:383-393).
@@ -734,11 +824,18 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
             wts = lu.member_sharded_sunrise_weights(logs, all_rd, agent, target_agent, ms, weighted_bellman_temp, discrete, slot)
         for m in members:
             m.bw = wts[ms.lo + m.i]
+    if c.packed:
+        # every member's gather has left its rows in the stacked batch: all E weight vectors from three launches
+        wts = lu.members_sunrise_weights(logs, c.xstack, c.S, agent, target_agent, weighted_bellman_temp, batch_size,
+                                         discrete, slot, c.pack_group)
+        for m in members:
+            m.bw = wts[m.i]
     for m in members:
         _member_step(m, c)
         m.rd["td_target"] = m.td
     if critic_clip:
-        _clip_and_step(adam, [(m.arena, ("critic", m.i), m.grads, m.ss) for m in members], critic_clip, None, ms)
+        _clip_and_step(adam, [(m.arena, ("critic", m.i), m.grads, m.ss) for m in members], critic_clip, None, ms,
+                       joint_ss=c.ss_all.view(-1) if c.ss_all is not None else None)
     # encoder: identity encoders carry no trainable tensor on this path (their dummy Linear(1,1)
     # never receives a gradient, nets/__init__.py:24), so encoder_optimizer.step() is a no-op.
     logs["losses/last_member_critic_td_error"] = slot[lu.L_TD_ERR]
@@ -756,7 +853,7 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     for m in members:
         if m.log_parts is None or logs_done_in_wgrad:
             continue
-        want = m.i == k
+        want = m.i == k and not c.members_form   # (a recordable ensemble update: the picked norm follows the loop)
         cap = engine.CAPTURE
         last = cap is not None and cap.feed and m is members[-1] and (done_norm or want)
         check(lib.ssac_critic_logs(m.log_parts.data_ptr(), m.log_nets, m.log_tiles, m.B, float(E_glob * m.n_glob),
@@ -766,7 +863,12 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
         if last:
             cap.published = True
         done_norm = done_norm or want
-    if not done_norm:
+    if not done_norm and c.members_form and engine.CAPTURE is not None:
+        # recorded: the pick of THIS update sits in the slot's aux word; the launch carries every member's buffer
+        table = (C.c_void_p * E)(*[m.ss.data_ptr() for m in members])
+        check(lib.ssac_group_norms_pick(table, E, engine.CAPTURE.pick_ptr, 1, ss_k.numel(), clip_ctl,
+                                        slot[lu.L_CRITIC_GN:].data_ptr(), st))
+    elif not done_norm:
         check(lib.ssac_group_norms(ss_k.data_ptr(), 1, ss_k.numel(), clip_ctl, slot[lu.L_CRITIC_GN:].data_ptr(), st))
     logs["gradients/critic_random_grad"] = slot[lu.L_CRITIC_GN]
     logs["gradients/encoder_criticloss_grad_norm"] = slot[lu.L_ENC_GN]
@@ -798,8 +900,14 @@ def _member_targets(m, c):
     # (ssac_gather) and the update has no gather launch
     dual_ok = (DUAL_LAUNCH and arena.fused_dbuf and not c.train_enc and not c.dr3_coeff and not c.discrete
                and _dual_fits(arena, c.batch_size) and not _split_forward(N, c.batch_size))
+    if c.members_form:
+        m.one_wg_chain = True
+        if engine.CAPTURE is not None:
+            engine.CAPTURE.set_member(m.i)   # the draw sites below hand out THIS member's block of the update's inputs
+    B_ = c.batch_size
     rd = m.rd = lu.sample_move_and_augment(buffer=c.buffer, batch_size=c.batch_size, augmenter=c.augmenter, aug_mix=c.aug_mix,
-                                           per=c.per, _defer_gather=dual_ok, _invariance=bool(c.encoder_lambda))
+                                           per=c.per, _defer_gather=dual_ok, _invariance=bool(c.encoder_lambda),
+                                           _xsa=c.xstack[m.i * B_:(m.i + 1) * B_] if c.xstack is not None else None)
     a, B = rd["primary_batch"][1], rd["primary_batch"][2].shape[0]
     m.B = B
     # The online critics' FORWARD does not depend on the TD target: on a second stream (a parallel graph
@@ -833,9 +941,12 @@ def _member_targets(m, c):
     c.all_rd.append(rd)
     if c.sm_table is not None:
         lu.member_sharded_softmax_scores(rd, agent, c.target_agent, c.ms, c.sm_table[m.ig])
+    if c.packed:
+        return   # (the weights of all member batches follow the loop: lu.members_sunrise_weights)
     m.bw = 1.0 if c.ms is not None else lu.compute_backup_weights(
         logs=c.logs, replay_dict=rd, agent=agent, target_agent=c.target_agent, weight_type=c.weight_type,
-        weight_temp=c.weighted_bellman_temp, batch_size=c.batch_size, discrete=c.discrete, _slot=c.slot)
+        weight_temp=c.weighted_bellman_temp, batch_size=c.batch_size, discrete=c.discrete, _slot=c.slot,
+        _w=ws.get(f"bw.w{m.i}", (B, 1)) if c.members_form else None)
 
 
 def _encoder_input(m, c):
@@ -971,7 +1082,13 @@ def _member_step(m, c):
         weight_ptr = wrow.data_ptr()
     pp, dopop = (popart.ptr if popart else 0), (1 if (popart and c.pop) else 0)
     ttot = engine.bf16_tiles_total(arena) if arena.shadow is not None else engine.wgrad_tiles_total(arena)
-    ss = m.ss = ws.get(f"cu.ss{i}", (N * ttot,))
+    if c.members_form:
+        if c.ss_all is None:
+            c.ss_all = ws.get("cu.ssall", (c.E, N * ttot))   # (the members' arenas have one shape: the
+        assert c.ss_all.shape[1] == N * ttot                  #  reference builds them in one constructor call)
+        ss = m.ss = c.ss_all[i]
+    else:
+        ss = m.ss = ws.get(f"cu.ss{i}", (N * ttot,))
     dq = ws.get(f"cu.dq{i}", (N, B, qd))
     grads = m.grads = ws.get(f"cu.g{i}", (arena.params.numel(),), zero=True) if c.critic_clip else None
     fused_form = arena.fused and not c.dr3_coeff

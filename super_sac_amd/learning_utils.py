@@ -168,6 +168,46 @@ def refresh_recordable(agent, buffer, per, dr3_coeff, launch_mode):
                                "bf16" in marks, launch_mode)
 
 
+# the backup weights of a recordable ensemble update (members_recordable) from ONE packed forward of every member's target
+# critics over the members' stacked batches + ONE ssac_members_sunrise_weights launch, instead of E forwards + E
+# ssac_ensemble_min_select + 1 ssac_sunrise_weights per member batch.  A module switch: tests/test_hip_members_recorded.py
+# (test_packed_weights_off_gives_the_same_bits) holds the two forms against each other.
+PACKED_WEIGHTS = True
+
+
+def members_recordable(launch_mode, ensemble_size, identity_encoder, kind, per, update_priorities, dr3, process_call, bf16,
+                       sharded, weight_type, weight_temp):
+    """May a critic update of an agent with ensemble_size > 1 be recorded (SUNRISE)?  Pure: tests/
+    test_members_recording_cpu.py walks every clause.  It holds for the library's launch lists, 2 .. MAX_MEMBERS members, an
+    identity encoder, a tanh-normal, deterministic or discrete head (not Beta), uniform sampling without a priority refresh
+    or DR3, a call that is not a continuous agent's with an exploration process (`process_call`), an fp32 agent, a rank that
+    is neither critic- nor member-sharded (`sharded`), and backup weights that are off or "sunrise".  Everything else --
+    "softmax" weights among it -- keeps the eager path.  The same answer selects the FORM of the eager calls of such an
+    agent (learning._critic_update_eager: stacked gathers, workspace-owned weights, the one-workgroup chained launch, the
+    picked gradient norm as a launch of its own), so warm-up, recorded and USE_GRAPHS = False updates leave the same bits."""
+    weights_off = weight_type is None or weight_temp is None
+    return bool(launch_mode == "list" and 2 <= ensemble_size <= MAX_MEMBERS and identity_encoder
+                and kind in ("stochastic", "deterministic", "discrete") and not per and not update_priorities and not dr3
+                and not process_call and not bf16 and not sharded and (weights_off or weight_type == "sunrise"))
+
+
+def members_call_recordable(agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type,
+                            weight_temp, launch_mode):
+    """members_recordable of a critic_update call.  The identity encoder has to sit on a buffer whose observations are one
+    vector array: only then does every member's replay gather leave [s | a] in place (no copy between the launches)."""
+    from . import parallel
+    marks = [o.__dict__.get("_ssac_precision") for o in list(agent.actors) + list(agent.critics)]
+    st = getattr(buffer, "_storage", None)
+    keys = list(st.s_stack.keys()) if st is not None else []
+    vec = len(keys) == 1 and st.s_stack[keys[0]].dim() == 2
+    kind = actor_kind(agent.actors[0])
+    return members_recordable(launch_mode, agent.ensemble_size, is_identity(agent.encoder) and vec, kind, bool(per),
+                              bool(update_priorities), bool(dr3_coeff),
+                              random_process is not None and not discrete and kind != "discrete", "bf16" in marks,
+                              parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
+                              weight_type, weight_temp)
+
+
 def recording_noise_buffers(kind, explore, refresh, in_kernel_noise):
     """The noise buffers a recorded critic update owns and refills on the host before every replay: (names filled before
     the REDQ subset is drawn, names filled after it), each in fill order, one rng.draw_normal_into call per name.  That is
@@ -338,11 +378,13 @@ class MemberUpdate:
     already), td_logs (its log words), td_keep (tensors the spec points into); bw (backup weights); branch (side stream);
     ss, grads, log_parts / log_nets / log_tiles, n_glob, logs_folded: what the clip and log launches read; td_rng: the
     ssac_rng (seed, counter address, offset) the TD target's noise was drawn with inside its launch, None when it came
-    from a buffer or the update has none -- a priority refresh in the same update draws its candidates at that number."""
+    from a buffer or the update has none -- a priority refresh in the same update draws its candidates at that number;
+    one_wg_chain (request): the chained launch keeps its one-workgroup form (recordable ensemble updates: the hand-off form
+    needs a per-replay tag their recording cannot reach, so their eager calls do without it too)."""
     __slots__ = ("i", "ig", "arena", "tag", "rd", "B", "want_fwd", "s_rep", "X", "ldx", "h1", "h2", "q", "want_bwd", "act",
                  "ld_act", "dz2u", "dz1u", "dz2_optional", "lazy_td", "fwd_done", "bwd_done", "w3_snapshot", "chain", "td",
                  "td_spec", "td_logs", "td_keep", "bw", "branch", "ss", "grads", "log_parts", "log_nets", "log_tiles",
-                 "n_glob", "logs_folded", "td_rng")
+                 "n_glob", "logs_folded", "td_rng", "one_wg_chain")
 
     def __init__(self, i, ig, arena):
         for f in self.__slots__:
@@ -423,7 +465,9 @@ def draw_augmentation_orders(augmenter, channels):
 
 
 def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _defer_gather=False,
-                            _invariance=False):
+                            _invariance=False, _xsa=None):
+    """``_xsa`` (critic_update, recordable ensemble updates): the (B, S + A) block of the members' stacked batch this
+    call's gather writes [s | a] to, instead of a tensor of its own (vector buffers)."""
     assert len(buffer) >= batch_size
     if not hasattr(buffer, "draw_uniform_indices") or not hasattr(augmenter, "single_shift"):
         # objects built by the reference's own classes (the shipped scripts construct them before main.super_sac
@@ -457,7 +501,8 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
     if vec:
         key = keys[0]
         S = st.s_stack[key].shape[1]
-        xsa = torch.empty(B, S + A, device=dev)
+        xsa = torch.empty(B, S + A, device=dev) if _xsa is None else _xsa
+        assert tuple(xsa.shape) == (B, S + A) and xsa.stride(1) == 1
         x1sa = torch.empty(B, S + A, device=dev)
         src = st.s_stack[key]
         cap = engine.CAPTURE
@@ -875,7 +920,8 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
     # which the launch reaches through the folded gather or the deferred-log struct -- a recording with neither keeps the
     # one-workgroup form)
     cap_ = engine.CAPTURE
-    pc_ok = CHAIN_PC and (cap_ is None or (gth is not None and gth.feed) or (cap_.feed and cap_.deferred is not None))
+    pc_ok = (CHAIN_PC and not m.one_wg_chain
+             and (cap_ is None or (gth is not None and gth.feed) or (cap_.feed and cap_.deferred is not None)))
     splits = 1
     if pc_ok and CHAIN_SPLIT and allow_split and c_arena.shadow is None:
         splits = int(lib.ssac_chain_target_splits(C.byref(ch["a_arena"].desc()), C.byref(t_arena.desc()),
@@ -1159,11 +1205,12 @@ def member_sharded_softmax_finish(logs, table, member_shard, weight_temp, slot):
 
 
 def compute_backup_weights(logs, replay_dict, agent, target_agent, weight_type, weight_temp, batch_size,
-                           discrete=False, _slot=None):
+                           discrete=False, _slot=None, _w=None):
     """learning_utils.py:357-398.  "sunrise": sigmoid(-std_k(Qbar_k(s, a)) T) + 0.5 over the members' TARGET critics
     (discrete: the taken action's column); "softmax": B softmax_b(-std_k(Q_k(s', a'_k)) T) with a'_k sampled from
     member k's ONLINE actor and scored by member k's ONLINE critics on the target encoder's s'.  Q_k = min over the
-    member's nets (agent.Critic.forward defaults, agent.py:22)."""
+    member's nets (agent.Critic.forward defaults, agent.py:22).  ``_w`` (critic_update, recordable ensemble updates): the
+    (B, 1) tensor the weights are written to -- a recorded launch needs an address that outlives the call."""
     if weight_type is None or weight_temp is None or agent.ensemble_size == 1:
         return 1.0
     assert weight_type in ("sunrise", "softmax"), f"unknown weight_type {weight_type!r}"
@@ -1192,7 +1239,7 @@ def compute_backup_weights(logs, replay_dict, agent, target_agent, weight_type, 
             check(lib.ssac_ensemble_min_select(q.data_ptr(), ar.n_nets, B, ar.out_dim,
                                                a.data_ptr() if discrete else 0, a.stride(0) if discrete else 0,
                                                qmin[k].data_ptr(), st))
-        w = torch.empty(B, 1, device=dev)
+        w = torch.empty(B, 1, device=dev) if _w is None else _w
         check(lib.ssac_sunrise_weights(qmin.data_ptr(), E, B, float(weight_temp), w.data_ptr(),
                                        slot[L_BW:].data_ptr(), st))
     else:
@@ -1230,6 +1277,70 @@ def compute_backup_weights(logs, replay_dict, agent, target_agent, weight_type, 
     for j, nm in enumerate(("mean", "max", "min", "std")):
         logs[f"bellman_weights/{nm}"] = slot[L_BW + j]
     return w
+
+
+def _fused_tile_rows(desc, n_rows, n_nets):
+    """row tile (16 or 32) ssac_mlp3_fwd_fused takes for this launch shape (its choice looks at the launch's size)"""
+    tiles = int(lib.ssac_fused_row_tiles(C.byref(desc), n_rows, n_nets))
+    return 16 if tiles == (n_rows + 15) // 16 else 32
+
+
+def members_pack_group(target_agent, E, B, dev):
+    """How many networks one packed forward of the members' target critics takes, or 0 when they keep their per-member
+    forwards.  The pack needs fused fp32 arenas of one shape; and the fused forward picks 16- or 32-row tiles by the size
+    of the launch, whose results differ in the last bits -- so the E N nets go out in groups small enough that the E B-row
+    launch takes the tile the B-row forward of one member's N nets takes (sunrise.gin's shape: 10 nets x 1 280 rows as
+    groups of 3).  A shape at which no group size does (very large E B) keeps the per-member forwards."""
+    arenas = [target_agent.critics[k].arena(dev) for k in range(E)]
+    a0 = arenas[0]
+    if not all(a.fused and a.shadow is None and (a.n_nets, a.in_dim, a.hidden, a.out_dim, a.stride) ==
+               (a0.n_nets, a0.in_dim, a0.hidden, a0.out_dim, a0.stride) for a in arenas):
+        return 0
+    desc = a0.desc()
+    want = _fused_tile_rows(desc, B, a0.n_nets)
+    group = min(E * a0.n_nets, MAX_PACK_NETS)
+    while group > 0 and _fused_tile_rows(desc, E * B, group) != want:
+        group -= 1
+    return group
+
+
+def members_sunrise_weights(logs, xstack, S, agent, target_agent, weight_temp, batch_size, discrete, slot, group):
+    """compute_backup_weights("sunrise") of ALL member batches at once (PACKED_WEIGHTS): xstack (E B, S + A) holds the
+    members' gathered [s | a] rows member-major.  Three launches: the E target-critic arenas into one pack
+    (ssac_polyak_multi, tau 1 -- inside every update, the targets move on Polyak steps a recording does not see), ONE
+    forward of the E N nets over the E B rows (`group` nets per launch: members_pack_group), ssac_members_sunrise_weights.  Returns
+    the (E, B) workspace tensor of the weights; the bellman_weights/* words are the last member's, as the reference's loop
+    leaves them."""
+    dev = xstack.device
+    ws = agent_ws(agent, dev)
+    st = engine.stream()
+    E, B = agent.ensemble_size, batch_size
+    arenas = [target_agent.critics[k].arena(dev) for k in range(E)]
+    a0 = arenas[0]
+    N, qd = a0.n_nets, a0.out_dim
+    per = N * a0.stride
+    pack = ws.get("bw.pack", (E * per,), zero=True)
+    t = (C.c_void_p * E)(*[pack.data_ptr() + 4 * k * per for k in range(E)])
+    s_ = (C.c_void_p * E)(*[a.params.data_ptr() for a in arenas])
+    cnt = (C.c_int64 * E)(*[per] * E)
+    check(lib.ssac_polyak_multi(t, s_, cnt, E, 1.0, st))
+    q = ws.get("bw.qpack", (E * N, E * B, qd))
+    ldx = xstack.stride(0)
+    for k0 in range(0, E * N, group):
+        k = min(group, E * N - k0)
+        desc = _lib.MlpDesc(pack.data_ptr() + 4 * k0 * a0.stride, a0.stride, k, a0.in_dim, a0.hidden, qd)
+        check(lib.ssac_mlp3_fwd_fused(C.byref(desc), 0, k, xstack.data_ptr(), ldx, 0, E * B, 0, 0, q[k0:k0 + k].data_ptr(),
+                                      st))
+    w = ws.get("bw.wall", (E, B))
+    check(lib.ssac_members_sunrise_weights(q.data_ptr(), E, N, B, qd, float(weight_temp),
+                                           xstack.data_ptr() + 4 * S if discrete else 0, ldx if discrete else 0,
+                                           w.data_ptr(), slot[L_BW:].data_ptr(), st))
+    for j, nm in enumerate(("mean", "max", "min", "std")):
+        logs[f"bellman_weights/{nm}"] = slot[L_BW + j]
+    return w
+
+
+MAX_PACK_NETS = 64   # SSAC_MAX_NETS: the networks of ONE packed forward launch
 
 
 def _min_over_nets(q, n, B, out):
