@@ -208,14 +208,13 @@ class _RecordedCritic:
     The inputs, made once by prepare() (feed is None before) -- what follows from the call and the agent: dev, log_ring
     (the device's LogRing), shard and n_critics (the GLOBAL ensemble); and the fixed addresses: layout (_SlotLayout); inbuf, the device block
     the first launch pulls a slot into, with its views idx_dev / ids_dev; stage, the host copy of the ring the slots are
-    composed in, with np_idx / np_i32 / np_draw; ring (_FeedRing); feed (the ssac_feed struct on the device); eps_dev
-    (injected noise, stochastic actors; else None); proc_dev (injected noise of the exploration process, continuous
-    agents called with one; else None: the call carries no process the update looks at); scale_ptr (device address of
-    the slot mirror's aux word, where ssac_explore_action reads the process's scale of the update; 0 without proc_dev);
-    refresh (the call refreshes the replay priorities: update_priorities=True), cand_dev (injected noise of the advantage
-    estimator's candidates, (N_SAMPLES * B, A) sample-major: a refresh on a tanh-normal policy; else None), fill (the
-    buffers _host_inputs refills per update under injected noise, (before, after) the subset draw:
-    lu.recording_noise_buffers);
+    composed in, with np_idx / np_i32 / np_draw; ring (_FeedRing); feed (the ssac_feed struct on the device); and what
+    the call's verdict (learning_utils.recording_verdict) asks for: n_members (E under verdict.members, else 1); eps_dev
+    (injected noise of the first member's head, stochastic actors; else None); proc_dev and scale_ptr (verdict.explore:
+    the process's injected noise, and the device address of the slot mirror's aux word, where ssac_explore_action reads
+    its scale; else None and 0); refresh (verdict.refresh) and cand_dev (the candidates' injected noise, (N_SAMPLES * B,
+    A) sample-major: a refresh on a tanh-normal policy; else None); fill (per member the buffers _host_inputs refills
+    under injected noise, (before, after) its subset draw: lu.recording_noise_buffers, one eps buffer per member);
     logblk (the log block the launches write); late_word (late-bound Polyak decision word, or None).
     What a recording produced, dropped by drop_recording() (graph is None: nothing recorded): graph (_LaunchList or
     CUDAGraph), dicts (the replay dicts handed back), members (the MemberUpdate records a replay reads), log_index
@@ -225,16 +224,14 @@ class _RecordedCritic:
     Progress: fast (the _FastStep over the recording's launch lists; None: not built, retired because a parameter moved, or
     dropped with its recording), calls (critic_update calls with this key, warm-up included), k (updates issued on the ring, by either
     replayer), path ("fast": the C step issued the last one, "slow": Python did), pending (log-ring slot of the newest
-    update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path).
-    Ensemble updates: n_members (E; 1 otherwise), eps_members (under injected noise, the E fixed (B, A) eps
-    buffers in member order; None for heads without noise), pick (the member learning.py:135 picked for the update about
-    to be issued: the slot's aux word)."""
+    update whose block has not been written yet, deferred logs only), events (slot-reuse events of the Python path), pick
+    (the member learning.py:135 picked for the update about to be issued: an ensemble's aux word)."""
     __slots__ = ("refs", "dev", "log_ring", "shard", "n_critics",
                  "layout", "inbuf", "idx_dev", "ids_dev", "stage", "np_idx", "np_i32", "np_draw", "ring", "feed", "eps_dev",
                  "proc_dev", "scale_ptr", "refresh", "cand_dev", "fill", "logblk", "late_word",
                  "graph", "dicts", "members", "log_index", "log_views", "in_kernel_noise", "deferred", "late_arenas",
                  "td_stats", "fast",
-                 "calls", "k", "path", "pending", "events", "n_members", "eps_members", "pick")
+                 "calls", "k", "path", "pending", "events", "n_members", "pick")
 
     def __init__(self, refs):
         for f in self.__slots__:
@@ -244,12 +241,13 @@ class _RecordedCritic:
         self.calls, self.k, self.path = 0, 0, "slow"
         self.n_members, self.pick = 1, 0
 
-    def prepare(self, agent, B, n_sub, explore=False, refresh=False, members=1):
+    def prepare(self, agent, B, n_sub, verdict):
         """One fixed device block holds the per-update inputs (_SlotLayout).  The host writes them into slot k % FEED_SLOTS
         of the input ring; the first recorded launch pulls the slot in (ssac_feed in include/ssac_hip.h), so an update is
-        ONE graph launch and no copy node.  members = E > 1: the layout of (E B, E n_sub) holds every member's index draw
-        and subset member-major -- B and n_sub below are the slot's."""
-        E = self.n_members = members
+        ONE graph launch and no copy node.  verdict.members, E > 1: the layout of (E B, E n_sub) holds every member's index
+        draw and subset member-major -- B and n_sub below are the slot's."""
+        E = self.n_members = agent.ensemble_size if verdict.members else 1
+        explore, refresh = verdict.explore, verdict.refresh
         rows = B
         B, n_sub = E * B, E * n_sub
         dev = self.dev = self.refs[3].device
@@ -268,23 +266,22 @@ class _RecordedCritic:
         self.ring = _FeedRing(FEED_SLOTS * lay.nbytes)
         self.events = [None] * (FEED_SLOTS // EVENT_EVERY)
         actor = agent.actors[0]
-        self.eps_dev = (torch.empty(rows, actor.action_size, device=dev) if lu.actor_kind(actor) == "stochastic" else None)
-        if E > 1 and self.eps_dev is not None:
-            self.eps_members = [self.eps_dev] + [torch.empty_like(self.eps_dev) for _ in range(E - 1)]
+        kind = lu.actor_kind(actor)
+        eps = [torch.empty(rows, actor.action_size, device=dev) if kind == "stochastic" else None for _ in range(E)]
+        self.eps_dev = eps[0]
         # an exploration process inside the update (TD3 / DDPG / AWAC): its noise, and where its scale arrives
         self.proc_dev = torch.empty(B, actor.action_size, device=dev) if explore else None
         self.scale_ptr = self.inbuf.data_ptr() + lay.aux_off if explore else 0
         # a priority refresh inside the update (AWAC / AFBC): the candidates' noise, one block of B rows per sample
-        kind = lu.actor_kind(actor)
-        self.refresh = bool(refresh)
+        self.refresh = refresh
         n_cand = adv_estimator.N_SAMPLES
         self.cand_dev = (torch.empty(n_cand * B, actor.action_size, device=dev)
                          if refresh and kind == "stochastic" else None)
-        named = {"eps": self.eps_dev, "proc": self.proc_dev}
+        named = {"proc": self.proc_dev}
         if self.cand_dev is not None:
             named.update({f"cand{k}": self.cand_dev[k * B:(k + 1) * B] for k in range(n_cand)})
-        self.fill = tuple([named[n_] for n_ in names]
-                          for names in lu.recording_noise_buffers(kind, explore, refresh, False))
+        before, after = lu.recording_noise_buffers(kind, explore, refresh, False)
+        self.fill = tuple(([dict(named, eps=e)[n_] for n_ in before], [named[n_] for n_ in after]) for e in eps)
         self.logblk = torch.zeros(lu.LOG_WIDTH, device=dev)
         # late-bound Polyak (include/ssac_hip.h): the decision word the update's first launch writes
         self.late_word = torch.zeros(4, dtype=torch.int32, device=dev) if lu.LATE_POLYAK else None
@@ -338,27 +335,14 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
     is_beta = lu.actor_kind(agent.actors[0]) == "beta"
     if is_beta and (shard is not None or parallel.member_shard_of(agent) is not None):
         beta.refuse("critic_update on a critic- or member-sharded agent")
-    members = agent.ensemble_size > 1 and lu.members_call_recordable(
-        agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type, weighted_bellman_temp,
-        LAUNCH_MODE)
-    graphable = (USE_GRAPHS and engine.CAPTURE is None and (agent.ensemble_size == 1 or members) and not per and not is_beta
-                 and parallel.member_shard_of(agent) is None
-                 # a priority refresh (AWAC / AFBC) is recorded when it runs as launches on the device trees
-                 and (not update_priorities or lu.refresh_recordable(agent, buffer, per, dr3_coeff, LAUNCH_MODE))
-                 and not dr3_coeff and lu.is_identity(agent.encoder)
-                 and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE) and torch.cuda.is_available()
-                 # critic-sharded ranks: recorded launch lists only (the collective sits between two segments),
-                 # continuous actions on the fused kernels (empty subset slots, in-launch TD target)
-                 and (shard is None or (LAUNCH_MODE == "list" and SHARDED_LISTS and not discrete
-                                        and not any(agent.popart)
-                                        and agent.critics[0].arena(log_alphas[0].device).fused)))
-    if not graphable:
-        return _critic_update_eager(**kw)
+    verdict = _verdict_of(kw)
+    if not verdict.record:
+        return _critic_update_eager(_verdict=verdict, **kw)
     key = (id(buffer), id(target_agent), id(critic_optimizer), batch_size, float(gamma), critic_clip,
            target_critic_ensemble_n, bool(pop), bool(discrete), id(log_alphas[0]), engine.USE_FUSED,
            id(random_process), noise_clip,   # (noise_clip is baked into the recorded argument bytes)
            bool(update_priorities))          # (the two call forms of an AFBC loop keep one recording each)
-    if members:
+    if verdict.members:
         key += (weight_type, weighted_bellman_temp)   # (an ensemble's backup weights are part of the recorded launches)
     cache = agent.__dict__.setdefault("_ssac_graphs", {})  # lives and dies with the agent
     gs = cache.get(key)
@@ -367,8 +351,13 @@ def critic_update(buffer, agent, target_agent, critic_optimizer, encoder_optimiz
         gs = cache[key] = _RecordedCritic((buffer, target_agent, critic_optimizer, log_alphas[0], random_process))
     gs.calls += 1
     if gs.calls <= GRAPH_WARMUP or len(buffer) < batch_size:
-        return _critic_update_eager(**kw)
-    return _critic_update_graphed(gs, kw)
+        return _critic_update_eager(_verdict=verdict, **kw)
+    return _critic_update_graphed(gs, kw, verdict)
+
+
+def _verdict_of(kw):
+    """what a critic_update(**kw) call may record, decided once per call (learning_utils.recording_verdict)"""
+    return lu.recording_verdict(lu.call_facts(kw, LAUNCH_MODE, USE_GRAPHS, SHARDED_LISTS))
 
 
 _fast_values = operator.itemgetter("batch_size", "gamma", "critic_clip", "encoder_clip", "target_critic_ensemble_n",
@@ -388,53 +377,36 @@ def _slot_codes(row, ids, shard):
 
 
 def _host_inputs(gs, buffer, agent, in_kernel_noise):
-    """what the host contributes to one recorded update, whoever re-issues it: the reference's host-RNG draws in its order
-    (indices -> (augmentation: none here) -> injected noise -> REDQ subset of the GLOBAL ensemble), the update's log-ring
-    slot, a sharded rank's exchange check, the draw number of the agent's noise stream (one draw per update, as eager)"""
-    lay = gs.layout
-    if gs.n_members > 1:
-        return _host_inputs_members(gs, buffer, agent, in_kernel_noise)
+    """what the host contributes to one recorded update, whoever re-issues it: every host-RNG draw of the update in the
+    reference's order -- per member its indices -> (augmentation: none here) -> its injected noise -> its REDQ subset of
+    the GLOBAL ensemble, into the member's block of the slot; behind the last member the one whose gradient norm is logged
+    (learning.py:135: gs.pick, an ensemble's aux word) and a refresh's member pick --, the update's log-ring slot, a sharded
+    rank's exchange check, the draw number of the agent's noise stream (one draw per member step, as eager)"""
+    lay, E = gs.layout, gs.n_members
+    B, n = lay.B // E, lay.n_sub // E
     if gs.refresh:
         # the recorded ssac_per_assign checks priority > 0 on the device: what the last update found is raised now
         buffer._per._raise_pending()
-    buffer.total_sample_calls += 1
-    idx_cpu = rng.draw_indices(len(buffer), lay.B)
-    before, after = ((), ()) if in_kernel_noise else gs.fill
-    for buf in before:
-        # injected noise (parity tests) goes straight into the update's input buffers: the head's eps, behind it the
-        # exploration process's (learning_utils.py:331-335)
-        rng.draw_normal_into(buf)
-    ids = rng.draw_subset(gs.n_critics, lay.n_sub)
-    for buf in after:
-        rng.draw_normal_into(buf)  # ... and the estimator's candidates of a priority refresh (adv_estimator.py:58-79)
+    rows, ids = [], []
+    for i in range(E):
+        before, after = ((), ()) if in_kernel_noise else gs.fill[i]
+        buffer.total_sample_calls += 1
+        rows.append(rng.draw_indices(len(buffer), B))
+        for buf in before:
+            # injected noise (parity tests) goes straight into the update's input buffers: the head's eps, behind it the
+            # exploration process's (learning_utils.py:331-335)
+            rng.draw_normal_into(buf)
+        ids += rng.draw_subset(gs.n_critics, n)
+        for buf in after:
+            rng.draw_normal_into(buf)  # ... and the estimator's candidates of a priority refresh (adv_estimator.py:58-79)
+    idx_cpu = rows[0] if E == 1 else torch.cat(rows)
+    pick = rng.choice(agent.critics)  # learning.py:135
+    gs.pick = 0 if E == 1 else next(j for j, c_ in enumerate(agent.critics) if c_ is pick)
+    if gs.refresh:
+        rng.choice(range(agent.ensemble_size))  # the refresh's member pick (learning_utils.py:289)
     slot_i = gs.log_ring.advance()
     if gs.shard is not None and gs.k % EVENT_EVERY == 0:
         parallel.check_exchange()
-    draw = 0
-    if in_kernel_noise:
-        ns = lu.noise_stream(agent, gs.dev)
-        draw = ns[1]
-        ns[1] += 1
-    return idx_cpu, ids, slot_i, draw
-
-
-def _host_inputs_members(gs, buffer, agent, in_kernel_noise):
-    """_host_inputs of an ensemble update: for every member in turn its indices, its injected eps (under a noise hook),
-    its subset -- the reference's order -- into the member's block of the stacked draw; behind the last subset the member
-    whose gradient norm is logged (learning.py:135: the slot's aux word, gs.pick).  The members' TD-target noise is drawn
-    in-kernel at draw numbers d0 .. d0 + E - 1 of the agent's stream, as E eager member steps consume it."""
-    lay, E = gs.layout, gs.n_members
-    B, n = lay.B // E, lay.n_sub // E
-    idx_cpu, ids = torch.empty(lay.B, dtype=torch.int64), []
-    for i in range(E):
-        buffer.total_sample_calls += 1
-        idx_cpu[i * B:(i + 1) * B] = rng.draw_indices(len(buffer), B)
-        if not in_kernel_noise and gs.eps_members is not None:
-            rng.draw_normal_into(gs.eps_members[i])
-        ids += rng.draw_subset(gs.n_critics, n)
-    pick = rng.choice(agent.critics)
-    gs.pick = next(j for j, c_ in enumerate(agent.critics) if c_ is pick)
-    slot_i = gs.log_ring.advance()
     draw = 0
     if in_kernel_noise:
         ns = lu.noise_stream(agent, gs.dev)
@@ -454,40 +426,29 @@ def _in_kernel_noise(gs, agent):
                                        and engine.bind_arena(actor, "self", [actor], gs.dev).fused)
 
 
-def _scale_bits(gs, kw):
-    """the slot's aux word of the update about to be issued: the process's scale NOW (the acting loop anneals it), as
-    the int32 with the float's bits; 0 for a recording without a process"""
+def _aux_word(gs, kw):
+    """the slot's aux word of the update about to be issued: the member whose gradient norm is logged (gs.pick) for an
+    ensemble, which carries no process (the gate); the process's scale NOW (the acting loop anneals it), as the int32
+    with the float's bits, for a recording with a process; 0 otherwise"""
+    if gs.n_members > 1:
+        return gs.pick
     if gs.proc_dev is None:
         return 0
     return struct.unpack("<i", struct.pack("<f", float(kw["random_process"].current_scale)))[0]
 
 
-def _aux_bits(gs, kw):
-    """the slot's aux word of the update about to be issued: an ensemble update carries no process (the gate), its word
-    names the member whose gradient norm is logged (gs.pick, drawn by _host_inputs_members); otherwise _scale_bits"""
-    return gs.pick if gs.n_members > 1 else _scale_bits(gs, kw)
-
-
 def _close_update(gs, agent, idx_cpu, ids, slot_i):
-    """the update has been issued: count it, keep the Python RNG stream in step, hand out this slot's log views"""
+    """the update has been issued: count it, hand every member's replay dict its rows and subset, hand out this slot's
+    log views.  Draws nothing (_host_inputs has made the update's picks)."""
     gs.k += 1
     if gs.deferred is not None:
         gs.pending = slot_i   # (the previous update's block is written by the launch just issued)
     E = gs.n_members
-    if E > 1:
-        # (learning.py:135's pick was drawn by _host_inputs_members, before the update was issued: nothing to draw here)
-        B, n = gs.layout.B // E, gs.layout.n_sub // E
-        idx_np = idx_cpu.numpy()
-        for i, rd in enumerate(gs.dicts):
-            rd["priority_idxs"] = idx_np[i * B:(i + 1) * B]
-            rd["_subset"] = ids[i * n:(i + 1) * n]
-        return dict(gs.views(slot_i)), gs.dicts
-    rng.choice(agent.critics)  # keep the Python RNG stream in step with learning.py:135
-    if gs.refresh:
-        rng.choice(range(agent.ensemble_size))  # ... and with the refresh's member pick (learning_utils.py:289)
-    rd = gs.dicts[0]
-    rd["priority_idxs"] = idx_cpu.numpy()
-    rd["_subset"] = ids
+    B, n = gs.layout.B // E, gs.layout.n_sub // E
+    idx_np = idx_cpu.numpy()
+    for i, rd in enumerate(gs.dicts):
+        rd["priority_idxs"] = idx_np[i * B:(i + 1) * B]
+        rd["_subset"] = ids[i * n:(i + 1) * n]
     return dict(gs.views(slot_i)), gs.dicts
 
 
@@ -573,7 +534,7 @@ class _FastStep:
         if gs.proc_dev is None and gs.n_members == 1:
             check(lib.ssac_step_run(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, draw, engine.stream()))
         else:
-            check(lib.ssac_step_run_aux(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, _aux_bits(gs, self.kw), draw,
+            check(lib.ssac_step_run_aux(self.handle, idx_cpu.data_ptr(), self.ids_c, slot_i, _aux_word(gs, self.kw), draw,
                                         engine.stream()))
         if self.late_arenas is not None:
             agent.critics[0].__dict__["_ssac_last_step"] = self   # a soft_update that follows needs no launch
@@ -586,7 +547,7 @@ class _FastStep:
             pass
 
 
-def _critic_update_graphed(gs, kw):
+def _critic_update_graphed(gs, kw, verdict):
     """one update of a recording from Python: the recording call itself, the hipGraph mode, lists with a collective
     between segments, and whatever the C step (_FastStep) does not serve"""
     buffer, agent = kw["buffer"], kw["agent"]
@@ -595,17 +556,15 @@ def _critic_update_graphed(gs, kw):
         torch.cuda.synchronize()
         gs.path = "slow"
     if gs.feed is None:
-        gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"],
-                   explore=kw["random_process"] is not None and not kw["discrete"], refresh=kw["update_priorities"],
-                   members=agent.ensemble_size)
+        gs.prepare(agent, kw["batch_size"], kw["target_critic_ensemble_n"], verdict)
     in_kernel_noise = _in_kernel_noise(gs, agent)
     if gs.graph is not None and gs.in_kernel_noise != in_kernel_noise:
         gs.drop_recording()
     _flush_other_recordings(agent, keep=gs if gs.graph is not None else None)
     idx_cpu, ids, slot_i, draw = _host_inputs(gs, buffer, agent, in_kernel_noise)
-    _write_slot(gs, idx_cpu, ids, slot_i, draw, _aux_bits(gs, kw))
+    _write_slot(gs, idx_cpu, ids, slot_i, draw, _aux_word(gs, kw))
     if gs.graph is None:
-        _record(gs, kw, idx_cpu, ids, in_kernel_noise)   # (the launches run now AND are recorded)
+        _record(gs, kw, verdict, idx_cpu, ids, in_kernel_noise)   # (the launches run now AND are recorded)
     else:
         gs.graph.replay()  # ONE host call re-issues the whole update
     _mark_group(gs)
@@ -643,14 +602,14 @@ def _mark_group(gs):
         gs.events[gi].record()
 
 
-def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
+def _record(gs, kw, verdict, idx_cpu, ids, in_kernel_noise):
     """run the update once with its launches recorded (a launch list, cut into segments around the collectives of a
     sharded rank, or a hipGraph) against the record's fixed-address inputs, and fill in what the recording produced"""
     buffer, agent, B, dev = kw["buffer"], kw["agent"], kw["batch_size"], gs.dev
     kind = lu.actor_kind(agent.actors[0])
     gs.in_kernel_noise = in_kernel_noise
-    # (the injected noise buffers in the reference's draw order: the head's eps, then the process's noise)
-    normals = gs.fill[0] if gs.n_members == 1 else (gs.eps_members or [])   # (an ensemble's: one eps buffer per member)
+    # (the injected noise buffers in the reference's draw order: member by member the head's eps, then the process's noise)
+    normals = [buf for before, _ in gs.fill for buf in before]
     ctx = engine.CaptureCtx(idx_cpu, gs.idx_dev, ids, gs.ids_dev, [] if in_kernel_noise else normals,
                             gs.logblk, feed=gs.feed.ptr)
     if gs.n_members > 1:
@@ -695,7 +654,7 @@ def _record(gs, kw, idx_cpu, ids, in_kernel_noise):
     gs.members = []   # the members' records: what a replay reads lives as long as the recording
 
     def body():
-        logs_, dicts_ = _critic_update_eager(_records=gs.members, **kw)
+        logs_, dicts_ = _critic_update_eager(_records=gs.members, _verdict=verdict, **kw)
         assert not ctx.pending_begin, "deferred ssac_begin_update was never issued"
         assert ctx.deferred_used == ctx.deferred_chain, "deferred log finalisation: chain / weight-gradient mismatch"
         gs.deferred = ctx.deferred if ctx.deferred_used else None
@@ -745,9 +704,11 @@ def _loss_folds(n_rows):
 def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_optimizer, log_alphas, batch_size, gamma,
                          critic_clip, encoder_clip, target_critic_ensemble_n, weighted_bellman_temp, weight_type, pop,
                          augmenter, encoder_lambda, random_process, noise_clip, aug_mix=0.75, discrete=False, per=False,
-                         update_priorities=False, dr3_coeff=0.0, _records=None):
-    """the ensemble-level flow; _records (a list, the recording's) receives the members' MemberUpdate records"""
+                         update_priorities=False, dr3_coeff=0.0, _records=None, _verdict=None):
+    """the ensemble-level flow; _records (a list, the recording's) receives the members' MemberUpdate records; _verdict:
+    critic_update's, made here when the call comes from elsewhere"""
     c = types.SimpleNamespace(**locals())   # the call: its arguments, and below what every member shares
+    verdict = _verdict if _verdict is not None else _verdict_of(vars(c))
     engine.require_gpu()
     if engine.CAPTURE is None:
         agent.critics[0].__dict__.pop("_ssac_last_step", None)
@@ -770,15 +731,12 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     st = c.st = engine.stream()
     c.train_enc = not lu.is_identity(agent.encoder)
     # head + exploration process as one launch (recorded updates, and eager ones on the agent's Philox stream)
-    c.explore = (random_process is not None and not discrete
-                 and lu.process_recordable(agent, random_process, discrete, per, LAUNCH_MODE))
+    c.explore = verdict.explore
     # An ensemble update that may be recorded takes ONE form in every call -- warm-up, recording, replay
     # and USE_GRAPHS = False alike: the members' gathers write into one stacked [s | a] batch, the backup weights and the
     # gradient-norm partials live in workspace tensors, the chained launch keeps its one-workgroup form and the picked
     # member's gradient norm is a launch of its own.
-    c.members_form = E > 1 and ms is None and lu.members_call_recordable(
-        agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type, weighted_bellman_temp,
-        LAUNCH_MODE)
+    c.members_form = verdict.members
     c.xstack = c.ss_all = None
     c.weights_on = weight_type is not None and weighted_bellman_temp is not None
     c.packed = False
@@ -874,7 +832,7 @@ def _critic_update_eager(buffer, agent, target_agent, critic_optimizer, encoder_
     logs["gradients/encoder_criticloss_grad_norm"] = slot[lu.L_ENC_GN]
     if update_priorities:  # learning.py:139-140: advantage-based priorities on the LAST member's batch
         lu.adjust_priorities(logs, members[-1].rd, agent, buffer, _member=members[-1],
-                             _recordable=lu.refresh_recordable(agent, buffer, per, dr3_coeff, LAUNCH_MODE))
+                             _recordable=verdict.refresh)
     return logs, [m.rd for m in members]
 
 

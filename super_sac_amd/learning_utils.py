@@ -136,15 +136,6 @@ def explore_recordable(kind, has_process, discrete, identity_encoder, ensemble_s
             and ensemble_size == 1 and not per and not sharded)
 
 
-def process_recordable(agent, random_process, discrete, per, launch_mode):
-    """explore_recordable of a critic_update call"""
-    from . import parallel
-    return explore_recordable(actor_kind(agent.actors[0]), random_process is not None, bool(discrete),
-                              is_identity(agent.encoder), agent.ensemble_size, bool(per),
-                              parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
-                              launch_mode)
-
-
 def priority_recordable(kind, per_on_device, identity_encoder, ensemble_size, per, dr3, sharded, bf16, launch_mode):
     """May a critic update called with update_priorities=True be recorded -- as far as the PRIORITY REFRESH is concerned
     (learning.critic_update's other clauses hold with or without one)?  Pure: tests/test_priority_recording_cpu.py walks
@@ -156,16 +147,6 @@ def priority_recordable(kind, per_on_device, identity_encoder, ensemble_size, pe
     (adjust_priorities): the warm-up calls and the recorded ones then follow one stream."""
     return bool(launch_mode == "list" and kind in ("stochastic", "deterministic", "discrete") and per_on_device
                 and identity_encoder and ensemble_size == 1 and not per and not dr3 and not sharded and not bf16)
-
-
-def refresh_recordable(agent, buffer, per, dr3_coeff, launch_mode):
-    """priority_recordable of a critic_update call"""
-    from . import parallel
-    marks = [o.__dict__.get("_ssac_precision") for o in list(agent.actors) + list(agent.critics)]
-    return priority_recordable(actor_kind(agent.actors[0]), bool(getattr(buffer, "per_on_device", False)),
-                               is_identity(agent.encoder), agent.ensemble_size, bool(per), bool(dr3_coeff),
-                               parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
-                               "bf16" in marks, launch_mode)
 
 
 # the backup weights of a recordable ensemble update (members_recordable) from ONE packed forward of every member's target
@@ -191,21 +172,58 @@ def members_recordable(launch_mode, ensemble_size, identity_encoder, kind, per, 
                 and not process_call and not bf16 and not sharded and (weights_off or weight_type == "sunrise"))
 
 
-def members_call_recordable(agent, buffer, random_process, discrete, per, update_priorities, dr3_coeff, weight_type,
-                            weight_temp, launch_mode):
-    """members_recordable of a critic_update call.  The identity encoder has to sit on a buffer whose observations are one
-    vector array: only then does every member's replay gather leave [s | a] in place (no copy between the launches)."""
+CallFacts = collections.namedtuple(
+    "CallFacts", "launch_mode kind discrete has_process identity_encoder vector_obs ensemble_size per per_on_device "
+                 "update_priorities dr3 bf16 critic_sharded member_sharded popart arena_fused weight_type weight_temp "
+                 "use_graphs capture cuda sharded_lists")
+Verdict = collections.namedtuple("Verdict", "record explore refresh members")
+
+
+def call_facts(kw, launch_mode, use_graphs, sharded_lists):
+    """What the gates of a critic_update(**kw) call look at, read off the agent and the buffer HERE and nowhere else.
+    vector_obs: the buffer's observations are one vector array (only then does every member's replay gather leave [s | a]
+    in place); bf16: some actor or critic carries the "_ssac_precision" mark; arena_fused: filled for critic-sharded
+    agents only -- arena() binds, and an unsharded agent's gate never asked."""
     from . import parallel
+    agent, buffer = kw["agent"], kw["buffer"]
     marks = [o.__dict__.get("_ssac_precision") for o in list(agent.actors) + list(agent.critics)]
     st = getattr(buffer, "_storage", None)
     keys = list(st.s_stack.keys()) if st is not None else []
-    vec = len(keys) == 1 and st.s_stack[keys[0]].dim() == 2
-    kind = actor_kind(agent.actors[0])
-    return members_recordable(launch_mode, agent.ensemble_size, is_identity(agent.encoder) and vec, kind, bool(per),
-                              bool(update_priorities), bool(dr3_coeff),
-                              random_process is not None and not discrete and kind != "discrete", "bf16" in marks,
-                              parallel.shard_of(agent) is not None or parallel.member_shard_of(agent) is not None,
-                              weight_type, weight_temp)
+    critic_sharded = parallel.shard_of(agent) is not None
+    return CallFacts(
+        launch_mode, actor_kind(agent.actors[0]), bool(kw["discrete"]), kw["random_process"] is not None,
+        is_identity(agent.encoder), len(keys) == 1 and st.s_stack[keys[0]].dim() == 2, agent.ensemble_size,
+        bool(kw["per"]), bool(getattr(buffer, "per_on_device", False)), bool(kw["update_priorities"]),
+        bool(kw["dr3_coeff"]), "bf16" in marks, critic_sharded, parallel.member_shard_of(agent) is not None,
+        any(agent.popart),
+        bool(critic_sharded and agent.critics[0].arena(kw["log_alphas"][0].device).fused),
+        kw["weight_type"], kw["weighted_bellman_temp"], bool(use_graphs), engine.CAPTURE is not None,
+        torch.cuda.is_available(), bool(sharded_lists))
+
+
+def recording_verdict(f):
+    """CallFacts -> Verdict, pure (tests/test_recording_verdict_cpu.py walks the grid).  record: the call's launches are
+    recorded and re-issued (learning.critic_update); explore: head + exploration process run as one launch, recorded or
+    eager (explore_recordable); refresh: the call's priority refresh runs as launches on the device trees
+    (priority_recordable); members: an ensemble update takes the recordable form (members_recordable)."""
+    sharded = f.critic_sharded or f.member_sharded
+    process_ok = explore_recordable(f.kind, f.has_process, f.discrete, f.identity_encoder, f.ensemble_size, f.per, sharded,
+                                    f.launch_mode)
+    refresh = f.update_priorities and priority_recordable(f.kind, f.per_on_device, f.identity_encoder, f.ensemble_size,
+                                                          f.per, f.dr3, sharded, f.bf16, f.launch_mode)
+    members = members_recordable(f.launch_mode, f.ensemble_size, f.identity_encoder and f.vector_obs, f.kind, f.per,
+                                 f.update_priorities, f.dr3, f.has_process and not f.discrete and f.kind != "discrete",
+                                 f.bf16, sharded, f.weight_type, f.weight_temp)
+    record = bool(
+        f.use_graphs and not f.capture and (f.ensemble_size == 1 or members) and not f.per and f.kind != "beta"
+        and not f.member_sharded
+        # a priority refresh (AWAC / AFBC) is recorded when it runs as launches on the device trees
+        and (refresh or not f.update_priorities) and not f.dr3 and f.identity_encoder and process_ok and f.cuda
+        # critic-sharded ranks: recorded launch lists only (the collective sits between two segments), continuous
+        # actions on the fused kernels (empty subset slots, in-launch TD target)
+        and (not f.critic_sharded or (f.launch_mode == "list" and f.sharded_lists and not f.discrete and not f.popart
+                                      and f.arena_fused)))
+    return Verdict(record, f.has_process and not f.discrete and process_ok, refresh, members)
 
 
 def recording_noise_buffers(kind, explore, refresh, in_kernel_noise):
@@ -1375,7 +1393,7 @@ def adjust_priorities(logs, replay_dict, agent, buffer, _member=None, _recordabl
     o, a = replay_dict["primary_batch"][0], replay_dict["primary_batch"][1]
     cap = engine.CAPTURE
     if cap is not None:
-        # recorded: learning._close_update makes the reference's random.choice per update; the rows are the indices of
+        # recorded: learning._host_inputs makes the reference's random.choice per update; the rows are the indices of
         # THIS update in the recording's input block, the priorities the estimator's fixed workspace tensor
         assert _recordable and agent.ensemble_size == 1
         res = agent.adv_estimator.evaluate(o, a, 0, want=("prio",), _update=(_member.td_rng, cap.cand))

@@ -36,15 +36,18 @@ def test_the_aux_word_is_the_pad_behind_the_log_slot(B, n_sub):
 
 
 def test_the_scale_bits_round_trip():
-    """_scale_bits hands ssac_step_run_aux / _write_slot an int32 whose bytes are the float's"""
+    """_aux_word hands ssac_step_run_aux / _write_slot an int32 whose bytes are the float's; the picked member for an
+    ensemble; 0 for a recording with neither"""
     import types
     from super_sac_amd import learning as L
     for scale in (0.0, 1.0, 0.1, 0.7, 1e-3, 2.5):
-        gs = types.SimpleNamespace(proc_dev=object())
-        bits = L._scale_bits(gs, {"random_process": types.SimpleNamespace(current_scale=scale)})
+        gs = types.SimpleNamespace(proc_dev=object(), n_members=1)
+        bits = L._aux_word(gs, {"random_process": types.SimpleNamespace(current_scale=scale)})
         assert -2 ** 31 <= bits < 2 ** 31
         assert np.array([bits], np.int32).view(np.float32)[0] == np.float32(scale)
-    assert L._scale_bits(types.SimpleNamespace(proc_dev=None), {"random_process": None}) == 0
+    assert L._aux_word(types.SimpleNamespace(proc_dev=None, n_members=1), {"random_process": None}) == 0
+    assert L._aux_word(types.SimpleNamespace(proc_dev=None, n_members=3, pick=2), {"random_process": None}) == 2
+    assert L._aux_word(types.SimpleNamespace(proc_dev=None, n_members=1, pick=0), {}) == 0
 
 
 def _rule(kind, has_process, discrete, identity_encoder, E, per, sharded, launch_mode):

@@ -6,9 +6,9 @@
   geometry; member i owns rows [i B, (i + 1) B) of the index block and ids [i n_sub, (i + 1) n_sub) of the id block, the
   aux word (the member whose gradient norm is logged) sits behind the log slot, and engine.CaptureCtx.set_member hands out
   exactly those blocks.
-* learning._host_inputs_members -- the host draws of one recorded update -- against a plain re-enactment of the
-  reference's order on Python's `random` and torch's CPU generator: per member indices, then subset; behind the last
-  subset the pick of learning.py:135; learning._close_update draws nothing more."""
+* learning._host_inputs -- the host draws of one recorded update, one member or several -- against a plain re-enactment
+  of the reference's order on Python's `random` and torch's CPU generator: per member indices, then subset; behind the
+  last subset the pick of learning.py:135 and a refresh's member pick; learning._close_update draws nothing more."""
 import itertools
 import random
 import types
@@ -117,8 +117,17 @@ class _Ring:
         return self.k - 1
 
 
-@pytest.mark.parametrize("E,B,N,n_sub,seed", [(3, 64, 2, 2, 17), (5, 256, 2, 2, 42), (2, 5, 10, 3, 3)])
+@pytest.mark.parametrize("E,B,N,n_sub,seed", [(3, 64, 2, 2, 17), (5, 256, 2, 2, 42), (2, 5, 10, 3, 3), (1, 64, 2, 2, 17),
+                                              (1, 5, 10, 3, 3)])
 def test_the_picks_place_in_the_python_random_stream(E, B, N, n_sub, seed):
+    _the_picks_place(E, B, N, n_sub, seed, refresh=False)
+
+
+def test_the_picks_place_behind_a_priority_refresh():
+    _the_picks_place(1, 64, 2, 2, 42, refresh=True)
+
+
+def _the_picks_place(E, B, N, n_sub, seed, refresh):
     from super_sac_amd import learning as L
     rows = 1000
     critics = [object() for _ in range(E)]
@@ -126,21 +135,22 @@ def test_the_picks_place_in_the_python_random_stream(E, B, N, n_sub, seed):
 
     class _Buf:
         total_sample_calls = 0
+        _per = types.SimpleNamespace(_raise_pending=lambda: None)
 
         def __len__(self):
             return rows
     buffer = _Buf()
-    gs = types.SimpleNamespace(layout=L._SlotLayout(E * B, E * n_sub), n_members=E, eps_members=None, n_critics=N,
-                               log_ring=_Ring(), dev=None, pick=None, refresh=False, shard=None, k=0, deferred=None,
-                               dicts=[{} for _ in range(E)], views=lambda slot_i: {"slot": slot_i})
+    gs = types.SimpleNamespace(layout=L._SlotLayout(E * B, E * n_sub), n_members=E, fill=(([], []),) * E, n_critics=N,
+                               log_ring=_Ring(), dev=None, pick=None, refresh=refresh, shard=None, k=0, deferred=None,
+                               proc_dev=None, dicts=[{} for _ in range(E)], views=lambda slot_i: {"slot": slot_i})
     random.seed(seed); torch.manual_seed(seed)
     got = []
     for _ in range(4):
         idx_cpu, ids, slot_i, draw = L._host_inputs(gs, buffer, agent, False)
-        assert L._aux_bits(gs, {}) == gs.pick and draw == 0
+        assert L._aux_word(gs, {}) == (gs.pick if E > 1 else 0) and draw == 0
         state = (random.getstate(), torch.get_rng_state())
         logs, dicts = L._close_update(gs, agent, idx_cpu, ids, slot_i)
-        # _close_update draws nothing: the pick was made before the update was issued
+        # _close_update draws nothing: the picks were made before the update was issued
         assert random.getstate() == state[0] and torch.equal(torch.get_rng_state(), state[1])
         for i, rd in enumerate(dicts):
             assert rd["priority_idxs"].tolist() == idx_cpu[i * B:(i + 1) * B].tolist()
@@ -148,7 +158,8 @@ def test_the_picks_place_in_the_python_random_stream(E, B, N, n_sub, seed):
         got.append((idx_cpu.clone(), list(ids), gs.pick, slot_i))
     after = (random.getstate(), torch.get_rng_state())
     assert buffer.total_sample_calls == 4 * E and gs.k == 4
-    # ---- the reference's order, re-enacted: per member torch.randint then random.sample; random.choice last
+    # ---- the reference's order, re-enacted: per member torch.randint then random.sample; random.choice last, and behind
+    # it the member pick of a priority refresh
     random.seed(seed); torch.manual_seed(seed)
     for u, (idx_cpu, ids, pick, slot_i) in enumerate(got):
         want_idx, want_ids = [], []
@@ -156,5 +167,7 @@ def test_the_picks_place_in_the_python_random_stream(E, B, N, n_sub, seed):
             want_idx.append(torch.randint(rows, (B,)))
             want_ids += random.sample(range(N), k=n_sub)
         want_pick = critics.index(random.choice(critics))
+        if refresh:
+            random.choice(range(1))
         assert torch.equal(idx_cpu, torch.cat(want_idx)) and ids == want_ids and pick == want_pick and slot_i == u
     assert random.getstate() == after[0] and torch.equal(torch.get_rng_state(), after[1])
