@@ -416,14 +416,14 @@ def _host_inputs(gs, buffer, agent, in_kernel_noise):
 
 
 def _in_kernel_noise(gs, agent):
-    """does a recording of gs draw its action noise inside its launches (the agent's Philox stream)?  The fused
-    actor-sample launch does (wide action heads take the per-layer path), and so does the head-only launch of an update
-    with an exploration process (ssac_explore_action), whatever the actor's arena looks like."""
-    if not (lu.IN_KERNEL_NOISE and rng.normal_is_stock()):
-        return False
-    actor = agent.actors[0]
-    return gs.proc_dev is not None or (lu.actor_kind(actor) == "stochastic"
-                                       and engine.bind_arena(actor, "self", [actor], gs.dev).fused)
+    """does a recording of gs draw its action noise inside its launches (the agent's Philox stream)?  The TD plan's noise
+    source (learning_utils.td_member_plan) on the recording's facts: the fused actor-sample launch does (wide action heads
+    take the per-layer path), and so does the head + process launch (ssac_explore_action), whatever the actor's arena
+    looks like -- a recorded call carries a process exactly when its verdict said explore (gs.proc_dev)."""
+    actor, explore = agent.actors[0], gs.proc_dev is not None
+    kind = lu.actor_kind(actor)
+    fused = kind == "stochastic" and not explore and engine.bind_arena(actor, "self", [actor], gs.dev).fused
+    return lu.td_member_plan(kind, explore, explore, fused, True).noise == "kernel"
 
 
 def _aux_word(gs, kw):
@@ -1965,9 +1965,7 @@ def alpha_update(buffer, agent, optimizers, batch_size, log_alphas, augmenter, a
                 # agent's Philox stream unless a noise hook is installed (then it is drawn like everywhere else)
                 scratch = ws.get(f"al.act{i}", (B, A))
                 if lu.IN_KERNEL_NOISE and rng.normal_is_stock():
-                    ns = lu.noise_stream(agent, dev)
-                    rs = _lib.Rng(ns[0], 0, ns[1])
-                    ns[1] += 1
+                    rs = lu.stream_rng(agent, dev)
                     eps_ptr, rng_ptr = 0, C.addressof(rs)
                 else:
                     eps = rng.draw_normal((B, A), dev)

@@ -10,6 +10,7 @@ import collections
 import ctypes as C
 import os
 import math
+import types
 
 import numpy as np
 import torch
@@ -119,6 +120,60 @@ def noise_stream(agent, device):
     if len(ns) < 3:   # (a checkpoint written before the actor updates numbered themselves)
         ns.append(0)
     return ns
+
+
+def stream_rng(agent, device):
+    """the ssac_rng of one update's in-kernel noise, ONE tick of the agent's stream: draw number = the host count, which
+    moves on (eager), or capture-time count + device-resident update counter (recorded: learning._host_inputs counts)"""
+    ns, cap = noise_stream(agent, device), engine.CAPTURE
+    if cap is not None:
+        return _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset)
+    ns[1] += 1
+    return _lib.Rng(ns[0], 0, ns[1] - 1)
+
+
+def skip_stream_tick(agent, device):   # (a member another rank owns: the tick its owner's stream_rng takes)
+    if engine.CAPTURE is None:
+        noise_stream(agent, device)[1] += 1
+
+
+TdPlan = collections.namedtuple("TdPlan", "head launch noise draws use_entropy")
+
+
+def td_member_plan(kind, has_process, explore, actor_fused, capture, want_fwd=False, want_bwd=False, target_dbuf=False,
+                   target_scalar=False, target_sharded=False, in_kernel=None):
+    """Which head produces a' of one member's TD target, in which launch, with noise from where, consuming which host
+    draws -- decided HERE for compute_td_targets, skip_td_draws, learning._in_kernel_noise and recording_noise_buffers.
+    Pure, of plain values (tests/test_td_plan_cpu.py walks the cross product); CHAIN_LAUNCH, IN_KERNEL_NOISE and the
+    generator are read at call time (in_kernel: asked as if they said so).  explore: the verdict's flag; capture: a
+    recording is open; want_fwd / want_bwd: the member's requests; target_*: the target critics' arena is fused_dbuf, has
+    out_dim 1, belongs to a critic-sharded agent.
+    head: "discrete" | "beta" | "explore" (head + process: ssac_explore_action) | "tanh_normal" | "deterministic".
+    launch of the head's forward + sample: "chain" (pending, issued with the REDQ subset as ssac_[bf16_]chain_update) |
+    "dual" (ssac_actor_sample_critic_fwd) | "fused" (ssac_actor_sample_fused) | "layers" (engine.mlp_forward, then a head
+    kernel).  noise: "kernel" (one tick of the agent's Philox stream, stream_rng) | "buffer" (draw_normal).  draws: what
+    the member consumes before its REDQ subset, in the reference's order, over "tick", "eps" (the head's), "proc" (the
+    process's); Beta's own draws stay inside beta.sample.  use_entropy: the 0/1 of ssac_td_target / ssac_td_spec."""
+    if in_kernel is None:
+        in_kernel = bool(IN_KERNEL_NOISE and rng.normal_is_stock())
+    proc = ("proc",) if has_process else ()
+    fuse_sample = kind == "stochastic" and actor_fused and not has_process
+    if kind in ("discrete", "beta"):
+        head, draws = kind, proc if kind == "beta" else ()
+    elif explore and has_process and (capture or in_kernel):
+        # every recorded update with a process, and -- one noise stream per run -- the eager calls of the same agents under
+        # the stock generator; under a noise hook the eager calls keep the two-kernel sequences (the parity tests' twin)
+        head, draws = "explore", ("tick",) if in_kernel else (("eps",) if kind == "stochastic" else ()) + proc
+    elif kind == "stochastic":
+        head, draws = "tanh_normal", (("tick",) if fuse_sample and in_kernel else ("eps",)) + proc
+    else:
+        head, draws = "deterministic", proc
+    # actor -> target critics chained inside one launch with the critics' forward + TD-independent backward
+    chain = bool(CHAIN_LAUNCH and fuse_sample and want_fwd and want_bwd and (not target_sharded or capture)
+                 and target_dbuf and target_scalar)
+    launch = "chain" if chain else "dual" if fuse_sample and want_fwd else "fused" if fuse_sample else "layers"
+    return TdPlan(head, launch, "kernel" if "tick" in draws else "buffer", draws,
+                  int(head not in ("discrete", "explore") and not has_process))
 
 
 def explore_recordable(kind, has_process, discrete, identity_encoder, ensemble_size, per, sharded, launch_mode):
@@ -236,7 +291,8 @@ def recording_noise_buffers(kind, explore, refresh, in_kernel_noise):
     test_priority_recording_cpu.py); learning._RecordedCritic fills its buffers by this list."""
     if in_kernel_noise:
         return [], []
-    before = (["eps"] if kind == "stochastic" else []) + (["proc"] if explore and kind != "discrete" else [])
+    # (a recorded call carries a process exactly when its verdict says explore; buffer noise: any arena draws the same)
+    before = list(td_member_plan(kind, explore, explore, False, True, in_kernel=False).draws)
     after = []
     if refresh and kind == "stochastic":
         from . import adv_estimator
@@ -392,7 +448,7 @@ class MemberUpdate:
     q); want_bwd -- the TD-independent backward may ride in the target launch (act, ld_act, dz2u, dz1u); dz2_optional --
     dz2u may stay inside the chained launch; lazy_td -- the TD target is left to the critic launch.  Outcomes, set by the
     launch that did the work: fwd_done, bwd_done; w3_snapshot (W3 as the chained launch saw it when it skipped dz2u, else
-    None); chain (arguments of a PENDING chained launch, None once issued); td with td_spec (ssac_td_spec; None: evaluated
+    None); chain (a PendingChain, None once issued); td with td_spec (ssac_td_spec; None: evaluated
     already), td_logs (its log words), td_keep (tensors the spec points into); bw (backup weights); branch (side stream);
     ss, grads, log_parts / log_nets / log_tiles, n_glob, logs_folded: what the clip and log launches read; td_rng: the
     ssac_rng (seed, counter address, offset) the TD target's noise was drawn with inside its launch, None when it came
@@ -413,6 +469,13 @@ class MemberUpdate:
 
 # target-critic outputs of a REDQ subset: q (n * parts, B, out); xchg_done: reduced over the critic-sharded ranks already
 SubsetQ = collections.namedtuple("SubsetQ", "q n parts xchg_done", defaults=(1, False))
+
+
+class PendingChain(collections.namedtuple("PendingChain", "a_arena s1_rep eps_ptr actor x1 S A logp rng_ptr keep")):
+    """MemberUpdate.chain: the actor half of a chained launch (TdPlan.launch "chain") as _actor_sample leaves it for
+    _launch_chain, which issues it once the REDQ subset is known; keep: what eps_ptr / rng_ptr point into"""
+    __slots__ = ()
+    bf16 = property(lambda self: self.a_arena.shadow is not None)   # the launch's bf16-operand family (set_precision)
 
 
 # actor sample -> target critics chained per workgroup, beside the critics' forward + unscaled backward: ONE launch
@@ -703,215 +766,171 @@ def compute_td_targets(logs, replay_dict, agent, target_agent, ensemble_idx, ens
     launches here take over the online critics' forward (ssac_actor_sample_critic_fwd) and the TD-independent half of their
     backward pass (ssac_target_fwd_critic_bwdu), and leave the final elementwise step with its three log values to the
     critic launch (``td_spec``; continuous actions, no PopArt); its outcomes say which of them did."""
-    m = _member
-    co_fwd = m if (m is not None and m.want_fwd) else None
-    o, a, r, o1, d = replay_dict["primary_batch"]
-    i = ensemble_idx
-    dev = r.device
-    ws = agent_ws(agent, dev)
-    slot = _slot if _slot is not None else log_block(dev)
-    actor = agent.actors[i]
-    popart = agent.popart[i]
-    log_alpha = log_alphas[i]
-    B = r.shape[0]
-    kind = actor_kind(actor)
-    st = engine.stream()
-
-    x1_pre = None
-    if not is_identity(target_agent.encoder) and kind != "discrete":
-        emb = target_agent.encoder.embedding_dim
-        x1_pre = ws.get(f"td.x1.{i}", (B, emb + actor.action_size))
-    s1_rep = encode(target_agent.encoder, o1, dst=x1_pre)
-    S = s1_rep.shape[1]
-    a_arena = engine.bind_arena(actor, "self", [actor], dev)
-    fuse_sample = kind == "stochastic" and a_arena.fused and random_process is None
-    # actor -> target critics chained inside one launch with the critics' forward + TD-independent backward
-    chain = (CHAIN_LAUNCH and fuse_sample and co_fwd is not None and m.want_bwd
-             and (parallel_shard_of(target_agent) is None or engine.CAPTURE is not None)
-             and target_agent.critics[i].arena(dev).fused_dbuf
-             and target_agent.critics[i].arena(dev).out_dim == 1)
-    if not (fuse_sample and co_fwd is not None):
-        ensure_gathered(replay_dict.get("_ssac"))  # (a deferred replay gather rides in the merged launch only)
-    if not fuse_sample:
-        _, _, aout = engine.mlp_forward(a_arena, s1_rep, _row_stride(s1_rep), 0, B, ws, f"td.a{i}",
-                                        save=False)
+    t = types.SimpleNamespace(**locals())   # the call: its arguments, and below what its steps share
+    m, i = _member, ensemble_idx
+    r = t.r = replay_dict["primary_batch"][2]
+    dev, B = t.dev, t.B = r.device, r.shape[0]
+    ws = t.ws = agent_ws(agent, dev)
+    t.slot = _slot if _slot is not None else log_block(dev)
+    actor = t.actor = agent.actors[i]
+    kind = t.kind = actor_kind(actor)
+    t.st, t.aout, t.x1, t.rs = engine.stream(), None, None, None
+    pre = not is_identity(target_agent.encoder) and kind != "discrete"   # the encoder writes straight into [s'|a']
+    x1_pre = ws.get(f"td.x1.{i}", (B, target_agent.encoder.embedding_dim + actor.action_size)) if pre else None
+    s1_rep = t.s1_rep = encode(target_agent.encoder, replay_dict["primary_batch"][3], dst=x1_pre)
+    S = t.S = s1_rep.shape[1]
+    a_arena = t.a_arena = engine.bind_arena(actor, "self", [actor], dev)
     t_arena = target_agent.critics[i].arena(dev)
-    from . import parallel
-    shard = parallel.shard_of(target_agent)
+    shard = parallel_shard_of(target_agent)
+    plan = t.plan = td_member_plan(kind, random_process is not None, _explore, a_arena.fused, engine.CAPTURE is not None,
+                                   m is not None and m.want_fwd, m is not None and m.want_bwd, t_arena.fused_dbuf,
+                                   t_arena.out_dim == 1, shard is not None)
+    bt = t.bt = replay_dict.get("_ssac")
+    if plan.launch in ("fused", "layers"):
+        ensure_gathered(bt)  # (a deferred replay gather rides in the merged launch only)
+    if plan.launch == "layers":
+        _, _, t.aout = engine.mlp_forward(a_arena, s1_rep, _row_stride(s1_rep), 0, B, ws, f"td.a{i}", save=False)
     N = t_arena.n_nets if shard is None else shard.num_critics  # the subset is drawn over the GLOBAL ensemble
     assert 0 < ensemble_n <= N
-    bt = replay_dict.get("_ssac")
-    logp = ws.get(f"td.logp{i}", (B,))
-    use_entropy = 0
-    # head + exploration process in ONE launch: every recorded update with a process, and -- one noise stream per run --
-    # the eager calls of the same agents while the noise comes from the engine's Philox stream (stock generator).  With a
-    # noise hook installed the eager calls keep the two-kernel sequences below: the parity tests hold the two against
-    # each other.
-    explore_launch = (_explore and random_process is not None and kind in ("stochastic", "deterministic")
-                      and (engine.CAPTURE is not None or (IN_KERNEL_NOISE and rng.normal_is_stock())))
-    if kind == "discrete":
-        ids = draw_subset(N, ensemble_n)
-        sq = _subset_q(ws, shard, t_arena, ids, s1_rep, _row_stride(s1_rep), B, dev, f"td.c{i}")
-        lp_ptr, qd = aout.data_ptr(), t_arena.out_dim
-        a_s1 = None
-    else:
-        A = actor.action_size
+    t.logp = ws.get(f"td.logp{i}", (B,))
+    if kind != "discrete":
+        A = t.A = actor.action_size
         if bt is not None and bt.x1sa is not None and s1_rep.data_ptr() == bt.x1sa.data_ptr():
-            x1 = bt.x1sa
-        elif x1_pre is not None:
-            x1 = x1_pre
+            t.x1 = bt.x1sa
         else:
-            x1 = _concat_buffer(ws, f"td.x1.{i}", s1_rep, A)
-        if kind == "beta":
-            # a' = a_dist_s1.sample() of the Beta head into the [s'|a'] buffer, log pi of that same x (the transform's
-            # cache, learning_utils.py:330-338)
-            beta.sample(agent, aout, B, A, "td", ws.get(f"td.xb{i}", (B, A)), x1, S + A, S, logp)
-            use_entropy = 1
-            if random_process is not None:
-                noise = draw_normal((B, A), dev)
-                check(lib.ssac_exploration_noise(x1.data_ptr(), S + A, S, noise.data_ptr(),
-                                                 float(random_process.current_scale),
-                                                 float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
-                use_entropy = 0
-        elif explore_launch:
-            td_rng = _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st)
+            t.x1 = x1_pre if x1_pre is not None else _concat_buffer(ws, f"td.x1.{i}", s1_rep, A)
+        if plan.noise == "kernel":
+            t.rs = stream_rng(agent, dev)
             if m is not None:
-                m.td_rng = td_rng
-        elif kind == "stochastic":
-            if fuse_sample and IN_KERNEL_NOISE and rng.normal_is_stock():
-                # the noise comes from the agent's Philox stream inside the launch: draw number = host count (eager)
-                # or capture-time count + the device-resident update counter (recorded launch list)
-                ns = noise_stream(agent, dev)
-                cap = engine.CAPTURE
-                rs = _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset) if cap is not None else _lib.Rng(ns[0], 0, ns[1])
-                if cap is None:
-                    ns[1] += 1
-                if m is not None:
-                    m.td_rng = (rs.seed, rs.counter, rs.offset)
-                _actor_sample(a_arena, s1_rep, B, 0, actor, x1, S, A, logp, C.addressof(rs), st, co_fwd,
-                              replay_dict, chain=chain, rng_keep=rs)
-                eps = None
-            else:
-                eps = draw_normal((B, A), dev)
-            if eps is not None and fuse_sample:
-                # actor forward + sample + log pi: ONE launch, a' lands in the [s'|a'] buffer
-                _actor_sample(a_arena, s1_rep, B, eps.data_ptr(), actor, x1, S, A, logp, 0, st, co_fwd,
-                              replay_dict, chain=chain, rng_keep=eps)
-            elif eps is not None:
-                check(lib.ssac_tanh_normal_fwd(aout.data_ptr(), 2 * A, eps.data_ptr(), B, A,
-                                               float(actor.log_std_low), float(actor.log_std_high),
-                                               x1.data_ptr(), S + A, S, logp.data_ptr(), st))
-            use_entropy = 1
-            if random_process is not None:
-                # exploration noise on the sampled action replaces the entropy term (learning_utils.py:331-335)
-                noise = draw_normal((B, A), dev)
-                check(lib.ssac_exploration_noise(x1.data_ptr(), S + A, S, noise.data_ptr(),
-                                                 float(random_process.current_scale),
-                                                 float(noise_clip) if noise_clip is not None else 0.0, B, A, st))
-                use_entropy = 0
-        else:
-            if random_process is not None:
-                noise = draw_normal((B, A), dev)
-                check(lib.ssac_det_action_fwd(aout.data_ptr(), A, 0, 0.0, noise.data_ptr(),
-                                              float(random_process.current_scale),
-                                              float(noise_clip) if noise_clip is not None else 0.0, B, A,
-                                              x1.data_ptr(), S + A, S, st))
-            else:
-                # no exploration process: a' = loc, and the entropy term is the log-density of Normal(loc, 1e-4) at its
-                # own mean (learning_utils.py:336-338 on distributions.py:107-114)
-                check(lib.ssac_det_action_fwd(aout.data_ptr(), A, 0, 0.0, 0, 0.0, 0.0, B, A, x1.data_ptr(), S + A, S, st))
-                check(lib.ssac_det_logprob(0, B, A, logp.data_ptr(), st))
-                use_entropy = 1
-        ids = draw_subset(N, ensemble_n)
-        sq = _subset_q(ws, shard, t_arena, ids, x1, S + A, B, dev, f"td.c{i}", m)
-        assert m is None or m.chain is None, "a chained launch is still pending"
-        lp_ptr, qd = logp.data_ptr(), 1
-        a_s1 = x1[:, S:]
-    q1 = sq.q
-    td = torch.empty(B, 1, device=dev)
+                m.td_rng = (t.rs.seed, t.rs.counter, t.rs.offset)
+        _TD_ACTION[plan.head](t)
+    ids = draw_subset(N, ensemble_n)
+    X, ldx = (s1_rep, _row_stride(s1_rep)) if kind == "discrete" else (t.x1, S + A)
+    sq = _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, f"td.c{i}", None if kind == "discrete" else m)
+    assert m is None or m.chain is None, "a chained launch is still pending"
+    td = _td_finish(t, sq, ids, t_arena.out_dim)
+    # (discrete: the logits; the reference returns probs here, only used by dr3)
+    return td, (s1_rep, t.aout[0] if kind == "discrete" else t.x1[:, S:])
+
+
+def _td_finish(t, sq, ids, out_dim):
+    """the TD target of the subset's outputs sq -- an ssac_td_spec record left to the critic launch where the member asks
+    for it, else the ssac_td_target launch --, its three logs, and the subset and [s'|a'] (DR3) into the replay dict"""
+    m, i, slot, r = t._member, t.ensemble_idx, t.slot, t.r
+    d, log_alpha, popart = t.replay_dict["primary_batch"][4], t.log_alphas[i], t.agent.popart[i]
+    lp_ptr, qd = (t.aout.data_ptr(), out_dim) if t.plan.head == "discrete" else (t.logp.data_ptr(), 1)
+    td = torch.empty(t.B, 1, device=t.dev)
     if m is not None and m.lazy_td and qd == 1 and not popart:
-        m.td_spec = _lib.TdSpec(q1.data_ptr(), lp_ptr, r.data_ptr(), d.data_ptr(), log_alpha.data_ptr(),
-                                td.data_ptr(), float(gamma), sq.n, use_entropy, sq.parts)
+        m.td_spec = _lib.TdSpec(sq.q.data_ptr(), lp_ptr, r.data_ptr(), d.data_ptr(), log_alpha.data_ptr(),
+                                td.data_ptr(), float(t.gamma), sq.n, t.plan.use_entropy, sq.parts)
         m.td_logs = slot[L_TD0 + 3 * i:]
-        m.td_keep = (q1, logp, r, d, log_alpha)
+        m.td_keep = (sq.q, t.logp, r, d, log_alpha)
     else:
         assert sq.parts == 1, "partial target Q needs the in-launch TD target (ssac_td_spec.n_parts)"
-        check(lib.ssac_td_target(q1.data_ptr(), sq.n, B, qd, lp_ptr, r.data_ptr(), d.data_ptr(),
-                                 log_alpha.data_ptr(), use_entropy, float(gamma),
-                                 popart.ptr if popart else 0, 1 if (popart and pop) else 0,
-                                 td.data_ptr(), slot[L_TD0 + 3 * i:].data_ptr(), st))
-    li = i if _log_idx is None else _log_idx   # (member-sharded ranks: the member's GLOBAL index names its logs)
-    logs[f"td_targets/mean_td_target_{li}"] = slot[L_TD0 + 3 * i]
-    logs[f"td_targets/std_td_target_{li}"] = slot[L_TD0 + 3 * i + 1]
-    logs[f"td_targets/entropy_bonus_{li}"] = slot[L_TD0 + 3 * i + 2]
-    replay_dict["_subset"] = ids
-    replay_dict["_x1"] = None if kind == "discrete" else x1  # [s' | a'] as fed to the target critics (DR3)
-    if kind == "discrete":
-        a_s1 = aout[0]  # logits; the reference returns probs here, only used by dr3
-    return td, (s1_rep, a_s1)
+        check(lib.ssac_td_target(sq.q.data_ptr(), sq.n, t.B, qd, lp_ptr, r.data_ptr(), d.data_ptr(),
+                                 log_alpha.data_ptr(), t.plan.use_entropy, float(t.gamma),
+                                 popart.ptr if popart else 0, 1 if (popart and t.pop) else 0,
+                                 td.data_ptr(), slot[L_TD0 + 3 * i:].data_ptr(), t.st))
+    li = i if t._log_idx is None else t._log_idx   # (member-sharded ranks: the member's GLOBAL index names its logs)
+    for j, name in enumerate(("mean_td_target", "std_td_target", "entropy_bonus")):
+        t.logs[f"td_targets/{name}_{li}"] = slot[L_TD0 + 3 * i + j]
+    t.replay_dict["_subset"], t.replay_dict["_x1"] = ids, t.x1
+    return td
 
 
-def _explore_action(agent, actor, kind, aout, x1, S, A, B, logp, random_process, noise_clip, dev, st):
-    """a' = process(head(aout)) into the [s'|a'] buffer in one launch (ssac_explore_action; the process replaces the
-    entropy term, learning_utils.py:331-335, so log pi is written but not used).  Noise: the agent's Philox stream -- draw
-    number = host count (eager) or the slot's draw number (recorded) -- under the stock generator; inside a recording made
-    under a noise hook, the record's fixed-address buffers (head eps first, then the process noise: the reference's draw
-    order).  Scale: by value (eager), or read by the launch from the slot's aux word (recorded)."""
-    cap = engine.CAPTURE
-    tanh_normal = kind == "stochastic"
-    rs, eps_ptr, noise_ptr = None, 0, 0
-    if IN_KERNEL_NOISE and rng.normal_is_stock():
-        ns = noise_stream(agent, dev)
-        rs = _lib.Rng(ns[0], cap.tick_ptr, cap.noise_offset) if cap is not None else _lib.Rng(ns[0], 0, ns[1])
-        if cap is None:
-            ns[1] += 1
-    else:
+def _scale_clip(t):
+    return float(t.random_process.current_scale), float(t.noise_clip) if t.noise_clip is not None else 0.0
+
+
+def _process_noise(t):
+    """exploration noise on the sampled action: it replaces the entropy term (learning_utils.py:331-335)"""
+    if t.random_process is not None:
+        noise = draw_normal((t.B, t.A), t.dev)
+        check(lib.ssac_exploration_noise(t.x1.data_ptr(), t.S + t.A, t.S, noise.data_ptr(), *_scale_clip(t), t.B, t.A, t.st))
+
+
+# ---- one body per TdPlan.head: a' into the [s'|a'] buffer t.x1, log pi into t.logp where the head has one
+def _td_action_beta(t):
+    # a' = a_dist_s1.sample() of the Beta head, log pi of that same x (the transform's cache, learning_utils.py:330-338)
+    beta.sample(t.agent, t.aout, t.B, t.A, "td", t.ws.get(f"td.xb{t.ensemble_idx}", (t.B, t.A)), t.x1, t.S + t.A, t.S, t.logp)
+    _process_noise(t)
+
+
+def _td_action_explore(t):
+    """a' = process(head(aout)) in one launch (ssac_explore_action; log pi is written but not used).  Noise: the update's
+    tick of the agent's Philox stream; inside a recording made under a noise hook, the record's fixed-address buffers (head
+    eps, then process noise: the reference's draw order).  Scale: by value, or read from the slot's aux word (recorded)."""
+    cap, A, tanh_normal = engine.CAPTURE, t.A, t.kind == "stochastic"
+    eps_ptr = noise_ptr = 0
+    if t.rs is None:
         assert cap is not None, "eager updates under a noise hook keep the two-kernel sequence"
         if tanh_normal:
-            eps_ptr = draw_normal((B, A), dev).data_ptr()
-        noise_ptr = draw_normal((B, A), dev).data_ptr()
+            eps_ptr = draw_normal((t.B, A), t.dev).data_ptr()
+        noise_ptr = draw_normal((t.B, A), t.dev).data_ptr()
     check(lib.ssac_explore_action(
-        aout.data_ptr(), 2 * A if tanh_normal else A, int(tanh_normal),
-        float(actor.log_std_low) if tanh_normal else 0.0, float(actor.log_std_high) if tanh_normal else 0.0,
-        eps_ptr, noise_ptr, C.addressof(rs) if rs is not None else 0, cap.scale_ptr if cap is not None else 0,
-        float(random_process.current_scale), float(noise_clip) if noise_clip is not None else 0.0, B, A,
-        x1.data_ptr(), S + A, S, logp.data_ptr() if tanh_normal else 0, st))
-    return (rs.seed, rs.counter, rs.offset) if rs is not None else None
+        t.aout.data_ptr(), 2 * A if tanh_normal else A, int(tanh_normal),
+        float(t.actor.log_std_low) if tanh_normal else 0.0, float(t.actor.log_std_high) if tanh_normal else 0.0,
+        eps_ptr, noise_ptr, C.addressof(t.rs) if t.rs is not None else 0, cap.scale_ptr if cap is not None else 0,
+        *_scale_clip(t), t.B, A, t.x1.data_ptr(), t.S + A, t.S, t.logp.data_ptr() if tanh_normal else 0, t.st))
 
 
-def _actor_sample(a_arena, s1_rep, B, eps_ptr, actor, x1, S, A, logp, rng_ptr, st, m, replay_dict,
-                  chain=False, rng_keep=None):
-    """actor forward + tanh-normal sample + log pi in ONE launch (a' lands in the [s'|a'] buffer), optionally -- m, the
-    member's record, asks for it -- with the online critics' forward as extra workgroups of the same launch."""
-    bt = replay_dict.get("_ssac")
-    if m is not None and chain:
-        # the whole TD-independent part of the update is ONE launch (ssac_chain_update), issued by _subset_q once the
-        # REDQ subset is known: nothing is launched here
-        m.chain = dict(a_arena=a_arena, s1_rep=s1_rep, eps_ptr=eps_ptr, actor=actor, x1=x1, S=S, A=A, logp=logp,
-                       rng_ptr=rng_ptr, rng_keep=rng_keep)
+def _td_action_tanh_normal(t):
+    eps = draw_normal((t.B, t.A), t.dev) if t.rs is None else None   # (None: the noise is drawn inside the launch)
+    if t.plan.launch == "layers":
+        check(lib.ssac_tanh_normal_fwd(t.aout.data_ptr(), 2 * t.A, eps.data_ptr(), t.B, t.A, float(t.actor.log_std_low),
+                                       float(t.actor.log_std_high), t.x1.data_ptr(), t.S + t.A, t.S, t.logp.data_ptr(), t.st))
+    else:
+        _actor_sample(t, eps)
+    _process_noise(t)
+
+
+def _td_action_deterministic(t):
+    noise = draw_normal((t.B, t.A), t.dev) if t.random_process is not None else None
+    process = (noise.data_ptr(), *_scale_clip(t)) if noise is not None else (0, 0.0, 0.0)
+    check(lib.ssac_det_action_fwd(t.aout.data_ptr(), t.A, 0, 0.0, *process, t.B, t.A, t.x1.data_ptr(), t.S + t.A, t.S, t.st))
+    if noise is None:
+        # a' = loc, and the entropy term is the log-density of Normal(loc, 1e-4) at its own mean (learning_utils.py:336-338
+        # on distributions.py:107-114)
+        check(lib.ssac_det_logprob(0, t.B, t.A, t.logp.data_ptr(), t.st))
+
+
+_TD_ACTION = {"beta": _td_action_beta, "explore": _td_action_explore, "tanh_normal": _td_action_tanh_normal,
+              "deterministic": _td_action_deterministic}
+
+
+def _own_gather(bt, x1, X, fp32_only):
+    """the ssac_gather struct when the launch's workgroups can fetch their replay rows themselves -- the deferred gather
+    of bt writes exactly the launch's [s'|a'] and [s|a] buffers --, else None with the gather done by a launch of its own"""
+    if (bt is not None and bt.pending is not None and x1.data_ptr() == bt.x1sa.data_ptr()
+            and X.data_ptr() == bt.xsa.data_ptr() and (not fp32_only or bt.pending["dtype"] == 0)):
+        return gather_struct(bt)
+    ensure_gathered(bt)
+    return None
+
+
+def _actor_sample(t, eps):
+    """actor forward + tanh-normal sample + log pi in ONE launch (a' lands in the [s'|a'] buffer), by TdPlan.launch on its
+    own ("fused"), with the online critics' forward as extra workgroups ("dual"), or left pending ("chain"); noise: the
+    buffer eps, or the update's tick t.rs"""
+    m, a_arena, s1_rep, x1, S, A, B = t._member, t.a_arena, t.s1_rep, t.x1, t.S, t.A, t.B
+    eps_ptr, rng_ptr = (eps.data_ptr(), 0) if eps is not None else (0, C.addressof(t.rs))
+    lo, hi = float(t.actor.log_std_low), float(t.actor.log_std_high)
+    if t.plan.launch == "chain":
+        # the whole TD-independent part of the update is ONE launch, issued by _subset_q once the REDQ subset is known
+        m.chain = PendingChain(a_arena, s1_rep, eps_ptr, t.actor, x1, S, A, t.logp, rng_ptr, eps if eps is not None else t.rs)
         m.fwd_done = True
-        return
-    if m is not None:
-        c_arena, X, ldx, h1, h2, q = m.arena, m.X, m.ldx, m.h1, m.h2, m.q
-        gth = None
-        if (bt is not None and bt.pending is not None and x1.data_ptr() == bt.x1sa.data_ptr()
-                and X.data_ptr() == bt.xsa.data_ptr()):
-            gth = gather_struct(bt)  # the workgroups fetch their rows from the replay arrays themselves
-        else:
-            ensure_gathered(bt)
+    elif t.plan.launch == "dual":
+        gth = _own_gather(t.bt, x1, m.X, False)
         with engine._timed("dual_fwd") as tm:
             for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (the launch is idempotent)
                 check(lib.ssac_actor_sample_critic_fwd(
-                    C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, eps_ptr,
-                    float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S, logp.data_ptr(),
-                    rng_ptr, C.byref(c_arena.desc()), X.data_ptr(), ldx, h1.data_ptr(), h2.data_ptr(),
-                    q.data_ptr(), C.byref(gth) if gth is not None else 0, st))
+                    C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, eps_ptr, lo, hi, x1.data_ptr(),
+                    S + A, S, t.logp.data_ptr(), rng_ptr, C.byref(m.arena.desc()), m.X.data_ptr(), m.ldx, m.h1.data_ptr(),
+                    m.h2.data_ptr(), m.q.data_ptr(), C.byref(gth) if gth is not None else 0, t.st))
         m.fwd_done = True
-        return
-    ensure_gathered(bt)
-    check(lib.ssac_actor_sample_fused(C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, eps_ptr,
-                                      float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S,
-                                      logp.data_ptr(), 0, 0, 0, rng_ptr, st))
+    else:
+        check(lib.ssac_actor_sample_fused(C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, eps_ptr, lo, hi,
+                                          x1.data_ptr(), S + A, S, t.logp.data_ptr(), 0, 0, 0, rng_ptr, t.st))
 
 
 # critic-sharded ranks: the exchange of the subset's target Q rides in the chained launch (a tail workgroup behind its
@@ -920,18 +939,12 @@ FUSE_XCHG = True
 
 
 def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=None):
-    """ssac_chain_update: the pending actor sample (m.chain, from _actor_sample), the target critics of the n subset
-    slots and the online critics' forward + TD-independent backward, ONE launch; returns the target outputs as a SubsetQ"""
+    """ssac_chain_update: the pending actor sample (m.chain: PendingChain), the target critics of the n subset slots and
+    the online critics' forward + TD-independent backward, ONE launch; returns the target outputs as a SubsetQ"""
     ch, m.chain = m.chain, None
     c_arena, h1, h2, dz2u, dz1u, Xc, ldxc, qc = m.arena, m.h1, m.h2, m.dz2u, m.dz1u, m.X, m.ldx, m.q
-    bt = m.rd.get("_ssac")
-    x1, S, A, actor = ch["x1"], ch["S"], ch["A"], ch["actor"]
-    gth = None
-    if (bt is not None and bt.pending is not None and x1.data_ptr() == bt.x1sa.data_ptr()
-            and Xc.data_ptr() == bt.xsa.data_ptr() and bt.pending["dtype"] == 0):
-        gth = gather_struct(bt)
-    else:
-        ensure_gathered(bt)
+    a_arena, s1_rep, x1, S, A, actor = ch.a_arena, ch.s1_rep, ch.x1, ch.S, ch.A, ch.actor
+    gth = _own_gather(m.rd.get("_ssac"), x1, Xc, True)
     # column-split target critics (producer / consumer form, fp32 family): every (slot, tile) gets `splits` consumer
     # workgroups and the slot's value arrives as that many partial sums -- read through ssac_td_spec.n_parts
     # (inside a recording the hand-off's tag must change per replay: it then comes from the input ring's update counter,
@@ -942,10 +955,9 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
              and (cap_ is None or (gth is not None and gth.feed) or (cap_.feed and cap_.deferred is not None)))
     splits = 1
     if pc_ok and CHAIN_SPLIT and allow_split and c_arena.shadow is None:
-        splits = int(lib.ssac_chain_target_splits(C.byref(ch["a_arena"].desc()), C.byref(t_arena.desc()),
+        splits = int(lib.ssac_chain_target_splits(C.byref(a_arena.desc()), C.byref(t_arena.desc()),
                                                   C.byref(c_arena.desc()), B, n))
     q1 = ws.get(tag + ".y", (n * splits, B, 1))
-    s1_rep = ch["s1_rep"]
     dl_ptr = 0
     if cap_ is not None and cap_.feed and cap_.deferred is not None:
         # recorded update: one extra workgroup of this launch writes the PREVIOUS update's log block to its ring slot
@@ -953,9 +965,7 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
         cap_.deferred_chain = True
     if c_arena.shadow is not None:
         # bf16-operand mode: the same launch on v_mfma_f32_32x32x16_bf16, fed from the arenas' bf16 shadows
-        a_arena = ch["a_arena"]
-        assert a_arena.shadow is not None and t_arena.shadow is not None, \
-            "bf16 mode: set_precision must cover the actor and the target agent too"
+        assert ch.bf16 and t_arena.shadow is not None, "bf16 mode: set_precision must cover the actor and the target agent too"
         bf = c_arena.bf_buffers(ws, "cu", B)
         # producer / consumer form (csrc/ssac_bf16.hip, bf_chain_pc_kernel), as below for the fp32 family
         ho = ws.get(tag + ".handoff", (B * A,), dtype=torch.int64, zero=True) if (pc_ok and A <= 8) else None
@@ -963,8 +973,8 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
             for _ in range(tm.reps):
                 check(lib.ssac_bf16_chain_update(
                     C.byref(a_arena.desc()), a_arena.shadow.data_ptr(), s1_rep.data_ptr(), _row_stride(s1_rep), B,
-                    ch["eps_ptr"], float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S,
-                    ch["logp"].data_ptr(), ch["rng_ptr"], C.byref(t_arena.desc()), t_arena.shadow.data_ptr(), ids_ptr, n,
+                    ch.eps_ptr, float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S,
+                    ch.logp.data_ptr(), ch.rng_ptr, C.byref(t_arena.desc()), t_arena.shadow.data_ptr(), ids_ptr, n,
                     q1.data_ptr(), C.byref(c_arena.desc()), c_arena.shadow.data_ptr(), Xc.data_ptr(), ldxc, qc.data_ptr(),
                     bf["h1t"].data_ptr(), bf["h2t"].data_ptr(), bf["dz2t"].data_ptr(), bf["dz1t"].data_ptr(),
                     bf["xt"].data_ptr(), C.byref(gth) if gth is not None else 0, dl_ptr,
@@ -981,9 +991,9 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
     with engine._timed("chain") as tm:
         for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (the launch is idempotent)
             check(lib.ssac_chain_update(
-                C.byref(ch["a_arena"].desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, ch["eps_ptr"],
+                C.byref(a_arena.desc()), s1_rep.data_ptr(), _row_stride(s1_rep), B, ch.eps_ptr,
                 float(actor.log_std_low), float(actor.log_std_high), x1.data_ptr(), S + A, S,
-                ch["logp"].data_ptr(), ch["rng_ptr"], C.byref(t_arena.desc()), ids_ptr, n,
+                ch.logp.data_ptr(), ch.rng_ptr, C.byref(t_arena.desc()), ids_ptr, n,
                 q1.data_ptr(), C.byref(c_arena.desc()), Xc.data_ptr(), ldxc, h1.data_ptr(), h2.data_ptr(),
                 qc.data_ptr(), 0 if skip_dz2 else dz2u.data_ptr(), dz1u.data_ptr(), w3s.data_ptr(),
                 C.byref(gth) if gth is not None else 0, dl_ptr, ho.data_ptr() if ho is not None else 0, splits,
@@ -994,32 +1004,33 @@ def _launch_chain(m, t_arena, ids_ptr, n, ws, tag, B, allow_split=True, xchg=Non
     return SubsetQ(q1, n, splits, xchg is not None and ho is not None)  # (... the launch reduced q1 over the ranks itself)
 
 
-def _target_fwd_critic_bwdu(m, t_arena, ids_ptr, n, X, ldx, B, q1):
-    """the n subset slots' target critics with the TD-independent half of member m's backward pass: ONE launch"""
-    check(lib.ssac_target_fwd_critic_bwdu(
-        C.byref(t_arena.desc()), ids_ptr, n, X.data_ptr(), ldx, B, q1.data_ptr(), C.byref(m.arena.desc()), m.h1.data_ptr(),
-        m.h2.data_ptr(), m.act.data_ptr(), m.ld_act, m.dz2u.data_ptr(), m.dz1u.data_ptr(), engine.stream()))
-    m.bwd_done = True
+def _target_q(m, t_arena, ids_dev, n, X, ldx, B, ws, tag, timed, allow_split=True, xchg=None):
+    """the target critics of the n subset slots ids_dev on X, as a SubsetQ: inside member m's pending chained launch, in
+    ONE launch with the TD-independent half of m's backward pass (once its forward is done and asks for it), or as a plain
+    forward.  timed: bench.py's live kernel timing may repeat the ridden launch (not in a sharded rank's recording)"""
+    if m is not None and m.chain is not None:
+        return _launch_chain(m, t_arena, ids_dev.data_ptr(), n, ws, tag, B, allow_split, xchg)
+    if m is not None and m.want_bwd and m.fwd_done and t_arena.fused_dbuf:
+        q1 = ws.get(tag + ".y", (n, B, t_arena.out_dim))
+        with engine._timed("dual_bwd" if timed else None) as tm:
+            for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
+                check(lib.ssac_target_fwd_critic_bwdu(
+                    C.byref(t_arena.desc()), ids_dev.data_ptr(), n, X.data_ptr(), ldx, B, q1.data_ptr(),
+                    C.byref(m.arena.desc()), m.h1.data_ptr(), m.h2.data_ptr(), m.act.data_ptr(), m.ld_act,
+                    m.dz2u.data_ptr(), m.dz1u.data_ptr(), engine.stream()))
+        m.bwd_done = True
+        return SubsetQ(q1, n)
+    _, _, q1 = engine.mlp_forward(t_arena, X, ldx, 0, B, ws, tag, net_ids=ids_dev, n_sel=n, save=False)
+    return SubsetQ(q1, n)
 
 
 def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, m=None):
     """target-critic outputs for the REDQ subset `ids`: SubsetQ(q, n, ...) with q of shape (n, B, out).  Sharded: forward of
     the locally owned subset members, elementwise min, MIN all-reduce of the (B x out) partial (the one real exchange step
-    of the critic update), n = 1.  m: the member's record -- its pending chained launch or ridden backward is issued here."""
-    ride = m is not None and m.want_bwd and m.fwd_done
+    of the critic update), n = 1.  m: the member's record -- its pending chained launch or ridden backward is issued here
+    (_target_q)."""
     if shard is None:
-        ids_dev = _upload_ids(ws, ids, dev, "sub")
-        if m is not None and m.chain is not None:
-            return _launch_chain(m, t_arena, ids_dev.data_ptr(), len(ids), ws, tag, B)
-        if ride and t_arena.fused_dbuf:
-            q1 = ws.get(tag + ".y", (len(ids), B, t_arena.out_dim))
-            with engine._timed("dual_bwd") as tm:
-                for _ in range(tm.reps):  # 1, except under bench.py's live kernel timing (idempotent launch)
-                    _target_fwd_critic_bwdu(m, t_arena, ids_dev.data_ptr(), len(ids), X, ldx, B, q1)
-            return SubsetQ(q1, len(ids))
-        _, _, q1 = engine.mlp_forward(t_arena, X, ldx, 0, B, ws, tag, net_ids=ids_dev, n_sel=len(ids),
-                                      save=False)
-        return SubsetQ(q1, len(ids))
+        return _target_q(m, t_arena, _upload_ids(ws, ids, dev, "sub"), len(ids), X, ldx, B, ws, tag, True)
     from . import parallel
     O = t_arena.out_dim
     qpart = ws.get(tag + ".qpart", (1, B, O))
@@ -1028,24 +1039,16 @@ def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, m=None):
         # recorded launch sequence: a fixed shape for every subset draw -- all len(ids) slots are forwarded, the
         # per-update device id block holds the LOCAL index of the members this rank owns and -1 for the others
         # (their outputs are +inf), and the collective runs between two recorded segments
-        n, parts = len(ids), 1
-        if m is not None and m.chain is not None:
-            # (partial sums only when the one-shot exchange will carry them: it sums a slot's parts before sending)
-            x_ = parallel._exchange if (FUSE_XCHG and parallel._exchange is not None
-                                        and m.chain["a_arena"].shadow is None
-                                        and n * B <= parallel._exchange.max_floats) else None
-            sq = _launch_chain(m, t_arena, cap.ids_dev.data_ptr(), n, ws, tag, B,
-                               allow_split=parallel._exchange is not None, xchg=x_)
-            if sq.xchg_done:
-                parallel.check_exchange()   # (of the exchanges issued so far: a host load, as all_reduce_min_owned does)
-                return sq
-            q1, parts = sq.q, sq.parts
-        elif ride and t_arena.fused_dbuf:
-            # ... and the TD-independent half of the local critics' backward pass rides in the same launch
-            q1 = ws.get(tag + ".y", (n, B, O))
-            _target_fwd_critic_bwdu(m, t_arena, cap.ids_dev.data_ptr(), n, X, ldx, B, q1)
-        else:
-            _, _, q1 = engine.mlp_forward(t_arena, X, ldx, 0, B, ws, tag, net_ids=cap.ids_dev, n_sel=n, save=False)
+        n, ch, xchg = len(ids), m.chain if m is not None else None, parallel._exchange
+        # (a chained launch: the exchange rides in it when it can; partial sums only when the one-shot exchange will
+        # carry them -- it sums a slot's parts before sending)
+        x_ = xchg if (ch is not None and FUSE_XCHG and xchg is not None and not ch.bf16
+                      and n * B <= xchg.max_floats) else None
+        sq = _target_q(m, t_arena, cap.ids_dev, n, X, ldx, B, ws, tag, False, allow_split=xchg is not None, xchg=x_)
+        if sq.xchg_done:
+            parallel.check_exchange()   # (of the exchanges issued so far: a host load, as all_reduce_min_owned does)
+            return sq
+        q1, parts = sq.q, sq.parts
         # MIN all-reduce of all n slots at once (n x B x O floats; slots this rank does not own hold +inf): the minimum
         # over the slots is taken where the TD target is evaluated, so no local min launch is needed
         if parallel.one_shot_ready(q1):
@@ -1075,18 +1078,16 @@ def _subset_q(ws, shard, t_arena, ids, X, ldx, B, dev, tag, m=None):
 # share class and shape).
 # ------------------------------------------------------------------------------------------
 def skip_td_draws(agent, actor, B, dev, n_critics, ensemble_n, random_process):
-    """the draws of compute_td_targets for one member: a' noise, exploration noise, then the REDQ subset"""
+    """the draws of compute_td_targets for one member: what its owner's plan lists (a' noise, exploration noise), then the
+    REDQ subset.  A member-sharded owner runs eagerly, without the head + process launch; no member request changes a
+    draw.  (The Beta head's own draws are not made here: critic_update refuses member-sharded Beta agents.)"""
     kind = actor_kind(actor)
-    if kind != "discrete":
-        A = actor.action_size
-        if kind == "stochastic":
-            fused = engine.bind_arena(actor, "self", [actor], dev).fused and random_process is None
-            if fused and IN_KERNEL_NOISE and rng.normal_is_stock():
-                noise_stream(agent, dev)[1] += 1
-            else:
-                draw_normal((B, A), dev)
-        if random_process is not None:
-            draw_normal((B, A), dev)
+    fused = kind == "stochastic" and engine.bind_arena(actor, "self", [actor], dev).fused
+    for draw in td_member_plan(kind, random_process is not None, False, fused, False).draws:
+        if draw == "tick":
+            skip_stream_tick(agent, dev)
+        else:
+            draw_normal((B, actor.action_size), dev)
     draw_subset(n_critics, ensemble_n)
 
 
@@ -1105,7 +1106,7 @@ def skip_alpha_draws(agent, actor, B, dev):
     if actor_kind(actor) != "stochastic":
         return
     if engine.bind_arena(actor, "self", [actor], dev).fused and IN_KERNEL_NOISE and rng.normal_is_stock():
-        noise_stream(agent, dev)[1] += 1
+        skip_stream_tick(agent, dev)
     else:
         draw_normal((B, actor.action_size), dev)
 
