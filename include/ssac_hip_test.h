@@ -70,8 +70,8 @@ int ssac_bf16_fwd_form(int form);
 
 /* ---- 2. lab hooks ------------------------------------------------------------------------------------------------ */
 #ifdef SSAC_LAB
-/* a device buffer of >= 16 int64: workgroup (0,0) of every fused launch records s_memtime() at its phase boundaries there;
- * NULL (default) disables it. */
+/* a device buffer of >= 16 int64 (>= 64 for the chained launches, whose roles stamp at slots 0.., 16.. and 32..): workgroup
+ * (0,0) of every fused launch records s_memtime() at its phase boundaries there; NULL (default) disables it. */
 int ssac_fused_debug_stamps(long long *dev_buf);
 int ssac_gemm_debug_stamps(long long *dev_buf); /* same for the weight-gradient GEMM launches */
 /* a device buffer of >= 64 int64: phase stamps of tile 0 of the bf16 launches (slots 0.. actor pass, 16.. target-critic

@@ -106,6 +106,38 @@ struct FusedArgs {
                                        // (fused_chain_pc_kernel): Y leaves as agent-scope stores and the workgroup counts itself in
 };
 
+// What the LEAN critic tile of the chained launch (fused_mlp_body, LEAN) reads of its FusedArgs, and nothing else, in the
+// order of first use.  FusedArgs is ~500 bytes and the critic role's copy is the third in fused_chain_pc_kernel's argument
+// segment: the ~30 words a lean tile needs lay scattered over it, and a workgroup's first instructions are the scalar
+// loads that collect them.  The kernel takes this block as one more by-value parameter BEHIND the others (the byte offsets
+// that recorded launch lists patch in ga / gt / gc stay where they are) and its lean critic tiles assemble their FusedArgs
+// from it (lean_view): hidden 256 and one head output are the instantiation's constants, so the six layer offsets follow
+// from in_dim.  slot_now is patched by a replay exactly like FusedArgs' (ssac_chain_update).
+struct CriticLeanArgs {
+    int xcd, n_rows;
+    const float *params; int64_t net_stride; int in_dim, gth_role;
+    const uint32_t *slot_now; const int64_t *idx; const ssac_feed *feed;
+    const float *s, *act; int64_t s_elems, a_elems;
+    const float *X; int64_t ldx;
+    float *xsa; int64_t ld_x;
+    float *H1, *H2, *W3S, *DZ2, *Y, *DZ1;
+    long long *dbg, *tl;   // LAB stamps
+};
+
+__device__ __forceinline__ FusedArgs lean_view(const CriticLeanArgs &c) {
+    FusedArgs g{};
+    g.params = c.params; g.net_stride = c.net_stride; g.in_dim = c.in_dim; g.hidden = 256; g.out_dim = 1;
+    g.off[0] = 0; g.off[1] = 256 * c.in_dim; g.off[2] = g.off[1] + 256; g.off[3] = g.off[2] + 256 * 256;
+    g.off[4] = g.off[3] + 256; g.off[5] = g.off[4] + 256;
+    g.X = c.X; g.ldx = c.ldx; g.n_rows = c.n_rows;
+    g.H1 = c.H1; g.H2 = c.H2; g.Y = c.Y; g.DZ2 = c.DZ2; g.DZ1 = c.DZ1; g.W3S = c.W3S;
+    g.xcd = c.xcd; g.slot_now = c.slot_now; g.gth_role = c.gth_role;
+    g.gth.idx = c.idx; g.gth.feed = c.feed; g.gth.s = c.s; g.gth.act = c.act; g.gth.s_elems = c.s_elems;
+    g.gth.a_elems = c.a_elems; g.gth.xsa = c.xsa; g.gth.ld_x = c.ld_x;
+    g.dbg = c.dbg; g.tl = c.tl;
+    return g;
+}
+
 // TD target of row b (see ssac_td_spec; same operation order as td_target_kernel in ssac_elementwise.hip)
 __device__ __forceinline__ float td_of_row(const FusedArgs &g, int b, int e) {
     if (!g.tds.q_t) return g.td[b];
@@ -944,7 +976,9 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
         constexpr int XR = TMR / 16;  // x-tile rows per thread: half-wave per row, 16 rows a pass
         const int xk = tid & 31, xr0 = tid >> 5;
         const int Sg = gidx ? (int)g.gth.s_elems : 0;
-        const bool actor_half = (g.gth_role & 1) != 0;  // roles 1, 3 (3: no start-of-update duties) and 5 (below)
+        // roles 1, 3 (3: no start-of-update duties) and 5 (below); never the lean critic tile (role 2 or none), whose view of
+        // its compact block must not be addressed through a run-time choice between two of its members
+        const bool actor_half = !LEAN && (g.gth_role & 1) != 0;
         // CONSUMER of a hand-off (MODE_PLAIN, role 5 / no gather): the input's state columns are fetched here -- s' rows
         // from the replay arrays or from X -- the action columns [S, S + A) stay ZERO in the x tile: fc1 runs on the state
         // part while the actor workgroup of the tile is still sampling, a' W1[:, S:]^T is added when it arrives
@@ -1127,6 +1161,7 @@ __device__ __forceinline__ void fused_mlp_body(const FusedArgs &g, float *smem, 
         }
         BSTAMP(2);
         if (NSPL == 1 && !CO) stage_first(st2, Ws, H, tid);
+        BSTAMP(12);
         if (FWD_BWD && !CO) {
             if (DIRECT_BWD) dnn.init(P + g.off[2], H, H, col0, lane);
             else st3.init(P + g.off[2], H, H, tid);
@@ -1717,7 +1752,7 @@ void fused_chain_kernel(FusedArgs ga, FusedArgs ga_rest, FusedArgs gt, FusedArgs
 template <int TC, bool ADBUF, bool AW3LATE = false, bool CLEAN = false>
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_pc_kernel(FusedArgs ga, FusedArgs gt, FusedArgs gc, int tiles_a, int tiles_t, int target_grid_x,
-                           int critic_grid_x, DeferredLogsArgs dl, int dl_on, XchgArgs xa, int xchg_on) {
+                           int critic_grid_x, DeferredLogsArgs dl, int dl_on, XchgArgs xa, int xchg_on, CriticLeanArgs cl) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int bid = blockIdx.x;
     SSAC_LAB_ONLY(if (gc.tl && threadIdx.x == 0 && bid < 512) gc.tl[2 * bid] = __builtin_amdgcn_s_memrealtime();)
@@ -1777,8 +1812,13 @@ void fused_chain_pc_kernel(FusedArgs ga, FusedArgs gt, FusedArgs gc, int tiles_a
         fused_mlp_body<MODE_PLAIN, 16, true, true>(gt, smem, bx, j, target_grid_x, (j == 0 && sp == 0) ? 16 : -1, sp);
     } else {
         const int c_lo = CRIT_FIRST ? tiles_a : t_hi;
-        const int L = ssac_xcd_contiguous_range(bid, c_lo, c_lo + n_crit, gc.xcd);
-        fused_mlp_body<MODE_CRITIC_U, TC, true, false, false, false, CLEAN>(gc, smem, L % critic_grid_x, L / critic_grid_x, critic_grid_x, 32);
+        if constexpr (CLEAN) {   // (the lean tile reads the compact block only: gc's ~500 bytes are not touched)
+            const int L = ssac_xcd_contiguous_range(bid, c_lo, c_lo + n_crit, cl.xcd);
+            fused_mlp_body<MODE_CRITIC_U, TC, true, false, false, false, true>(lean_view(cl), smem, L % critic_grid_x, L / critic_grid_x, critic_grid_x, 32);
+        } else {
+            const int L = ssac_xcd_contiguous_range(bid, c_lo, c_lo + n_crit, gc.xcd);
+            fused_mlp_body<MODE_CRITIC_U, TC, true, false, false, false, CLEAN>(gc, smem, L % critic_grid_x, L / critic_grid_x, critic_grid_x, 32);
+        }
     }
 #ifdef SSAC_LAB
     if (gc.tl && bid < 512) {
@@ -2043,7 +2083,7 @@ KernelFamily<FusedArgs, FusedArgs, int, int> DUAL{"fused_dual", {
 KernelFamily<FusedArgs, FusedArgs, FusedArgs, FusedArgs, int, int, int, DeferredLogsArgs, int> CHAIN{"fused_chain", {
     {16, FORM_DBUF, fused_chain_kernel<16, true>}, {32, FORM_DBUF, fused_chain_kernel<32, true>},
     {16, FORM_SINGLE, fused_chain_kernel<16, false>}, {32, FORM_SINGLE, fused_chain_kernel<32, false>}}};
-KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int, int, int, DeferredLogsArgs, int, XchgArgs, int> CHAIN_PC{"fused_chain_pc", {
+KernelFamily<FusedArgs, FusedArgs, FusedArgs, int, int, int, int, DeferredLogsArgs, int, XchgArgs, int, CriticLeanArgs> CHAIN_PC{"fused_chain_pc", {
     {16, FORM_DBUF, fused_chain_pc_kernel<16, true>}, {32, FORM_DBUF, fused_chain_pc_kernel<32, true>},
     {16, FORM_SINGLE, fused_chain_pc_kernel<16, false>}, {32, FORM_SINGLE, fused_chain_pc_kernel<32, false>},
     {16, FORM_LATE, fused_chain_pc_kernel<16, true, true>}, {32, FORM_LATE, fused_chain_pc_kernel<32, true, true>},
@@ -2310,8 +2350,15 @@ extern "C" int ssac_chain_update(const ssac_mlp *actor, const float *Xa, int64_t
             return ssac_check_launch("fused_chain_co");
         }
         const dim3 grid_pc(tgx + tiles_c + cgx * critics->n_nets + dl_on + xchg_on);
-        SSAC_LAUNCH(pc_kernel, grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on);
-        if (gather && gather->feed) patch_slots(3);   // ga, gt, gc
+        // the lean critic tiles' compact copy of gc (CriticLeanArgs; the other instantiations ignore the parameter)
+        const CriticLeanArgs cl{gc.xcd, gc.n_rows, gc.params, gc.net_stride, gc.in_dim, gc.gth_role, gc.slot_now, gc.gth.idx,
+                                gc.gth.feed, gc.gth.s, gc.gth.act, gc.gth.s_elems, gc.gth.a_elems, gc.X, gc.ldx, gc.gth.xsa,
+                                gc.gth.ld_x, gc.H1, gc.H2, gc.W3S, gc.DZ2, gc.Y, gc.DZ1, gc.dbg, gc.tl};
+        SSAC_LAUNCH(pc_kernel, grid_pc, dim3(NTHR), lds, st, ga, gt, gc, tgx, tiles_c, tgx, cgx, dl, dl_on, xa, xchg_on, cl);
+        if (gather && gather->feed) {
+            patch_slots(3);   // ga, gt, gc
+            ssac_record_slot_patch(11, offsetof(CriticLeanArgs, slot_now));   // ... and cl, the kernel's twelfth argument
+        }
         return ssac_check_launch("fused_chain_pc");
     }
     g_chain_lean_taken = 0;

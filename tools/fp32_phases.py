@@ -37,6 +37,8 @@ print("actor pass: tanh-normal sample per (row, dim) incl. publish", t[9] - t[7]
 row("target pass ", t, 16, names)
 print("actor start -> target pass end:", t[23] - t[0])
 row("critic WG   ", t, 32, names + ["loss", "head-bwd", "dgrad", "dz1-store"])
+# (stamp 12 of the critic tile: behind the staging store of W2's first chunk -- the store carries the wait for the chunk)
+print("critic WG: fc1's closing barrier -> W2's first chunk stored to LDS", t[44] - t[34], " rest of the fc1 epilogue", t[35] - t[44])
 row("wgrad tile 0", g, 0, ["operand issue + loss fold + first chunk", "K loop", "partials -> LDS", "adam epilogue"])
 print("wgrad tile 0 front (the role's first instruction -> stamp 0: argument words, addresses, the L2 touches):", g[0] - g[13],
       " tile in all", g[4] - g[13], " form taken (1 fixed-shape):", ssa._lib.lib.ssac_wgrad_fixed_taken())
