@@ -64,6 +64,14 @@ int ssac_chain_lean_taken(void);
 int ssac_wgrad_fixed(int on);
 /* which form the LAST merged weight-gradient launch took: 1 fixed-shape, 0 any other, -1 no launch yet. */
 int ssac_wgrad_fixed_taken(void);
+/* Write-through (16-byte `sc1`) stores for arrays that one update launch hands to the next and that no workgroup of the
+ * writing launch loads back (profiles/store_through.md).  Bit mask, default 1, -1 = the library's default:
+ *   bit 0  p, m, v and the Polyak target of the fc2 tiles of the fixed-shape weight-gradient launch (ssac_wgrad_fixed).
+ * Everything else keeps plain stores: the fc1 tiles' dword epilogue, the biases, the head workgroups, every other form of the
+ * launch.  Cache policy only: bit-identical results. */
+int ssac_store_through(int mask);
+/* the bits the LAST merged weight-gradient launch actually took (0: it was not the fixed form, or the switch was off) */
+int ssac_store_through_taken(void);
 /* large-batch form of ssac_bf16_mlp3_fwd: 1 (default) = the register-chained kernel where it applies, 0 = the streaming
  * kernel everywhere.  Same operands, same rounding points. */
 int ssac_bf16_fwd_form(int form);

@@ -268,7 +268,10 @@ struct LateTau { bool on; uint32_t bits; };
 // so everything derived from them folds at compile time; the flag adds the facts the values alone cannot tell: 1 = an fc2
 // tile (256 x 256: every column block exists, the 16-byte optimizer form, no bias gradient), 2 = an fc1 tile (one column
 // block of at most 32 columns: the waves of the right half never multiply); both: gradient-norm slots are present.
-template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false, int FIXED = 0>
+// WT (fixed form, fc2 tiles): the 16-byte optimizer stores -- p, m, v, target -- leave through write-through windows on the
+// tile's own 64 x 64 block of each arena (StoreThrough, ssac_internal.h).  A tile is the only reader and the only writer of
+// its block in this launch, and it has read it (opt_prefetch) before it stores; the next reader is the next launch.
+template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false, int FIXED = 0, bool WT = false>
 __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int bx, int by, int bz,
                                               float *late_rs, const LossFoldArgs &lf, int lf_mode,
                                               const LogFoldArgs &fold, int &last,
@@ -302,6 +305,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     const int e = bz;
     const int m0 = by * BM, n0 = bx * BN;
     static_assert(FIXED == 0 || (VECONLY && EPI == EPI_ADAM && KS == 4), "the fixed-shape form is the lean Adam kernel with four K-groups");
+    static_assert(!WT || FIXED == 1, "write-through optimizer stores: the fixed form's fc2 tiles (whole 64 x 64 blocks, 16-byte form)");
     // LEAN_HANDOFF: the fixed form's order of work behind the K loop (profiles/wgrad_handoff.md): partials parked in the
     // free staging buffer with no barrier in front, the optimizer stores issued next, the gradient norm's wave partials
     // (LDS words of their own, one barrier) behind them.  The general kernels keep the hand-off they had.
@@ -646,6 +650,20 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
                         pn[c] = adam_elem(p4[j][c], g4[j][c], m, v, ctl);
                         m4[j][c] = m; v4[j][c] = v;
                         tn[c] = t4[j][c] * (1.0f - tau) + pn[c] * tau;
+                    }
+                    if constexpr (WT) {
+                        // one window per arena over this tile's block, rows ldc apart, ending behind the block's last row
+                        // (every row and column of an fc2 tile exists: ok4 is true throughout); lane offset = its element
+                        const int64_t t0 = coff + (int64_t)m0 * g.ldc + n0;
+                        const uint32_t bytes = (uint32_t)((BM - 1) * g.ldc + BN) * 4u;
+                        const int id = tid_all + j * NT_ALL;
+                        const uint32_t o = (uint32_t)((id >> 4) * (int)g.ldc + (id & 15) * 4) * 4u;
+                        StoreThrough w;
+                        w.init(g.am + t0, bytes); w.store16(o, m4[j]);
+                        w.init(g.av + t0, bytes); w.store16(o, v4[j]);
+                        w.init(g.C + t0, bytes); w.store16(o, pn);
+                        if (pol) { w.init(g.tw + t0, bytes); w.store16(o, tn); }
+                        continue;
                     }
                     *reinterpret_cast<f4 *>(g.am + c4[j]) = m4[j];
                     *reinterpret_cast<f4 *>(g.av + c4[j]) = v4[j];
@@ -994,6 +1012,9 @@ __device__ __forceinline__ HeadWgradArgs wgrad_fixed_head(const WgradFixedArgs &
                          p.sumsq2, p.sumsq_stride, p.tw, p.tau, 1, o.b2};
 }
 
+// WT: the fc2 tiles write their optimizer state through (ens_gemm_body, WT) -- what a launch takes; <false> keeps plain stores
+// (ssac_store_through(0)).  One kernel per form, since a kernel holds one instantiation of the body per role.
+template <bool WT>
 __global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArgs p) {
     constexpr int KS = 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1033,7 +1054,7 @@ __global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArg
     } else if (bid < p.tiles0) {
         const GemmArgs g = wgrad_fixed_tile<1>(p);
         const int bz = bid / FX_TILES2, rem = bid % FX_TILES2;
-        ens_gemm_body<false, false, EPI_ADAM, KS, true, 1>(g, lds, rem % FX_GRID, rem / FX_GRID, bz, tab, p.lf, 1, p.fold, last, lt);
+        ens_gemm_body<false, false, EPI_ADAM, KS, true, 1, WT>(g, lds, rem % FX_GRID, rem / FX_GRID, bz, tab, p.lf, 1, p.fold, last, lt);
         drawn = true;
     } else {
         const GemmArgs g = wgrad_fixed_tile<2>(p);
@@ -1455,6 +1476,12 @@ bool lean_ok(const GemmArgs &g) {
 
 int g_wgrad_fixed = 1;          // ssac_wgrad_fixed: 0 = the merged launch never takes its fixed-shape form
 int g_wgrad_fixed_taken = -1;   // ssac_wgrad_fixed_taken: form of the last merged weight-gradient launch (1 fixed, 0 any other, -1 none yet)
+// ssac_store_through: bit 0 = the fixed form's fc2 tiles write p / m / v / target through (wgrad_fixed_kernel<true>).  On:
+// 47.09 -> 46.04 us per update on the headline, all of it in this launch (profiles/store_through.md; the same stores for
+// h1 / h2 / dz1u of the chained launch's critic tiles measured SLOWER and are not in the library).
+constexpr int STORE_THROUGH_WGRAD = 1, STORE_THROUGH_DEFAULT = STORE_THROUGH_WGRAD;
+int g_store_through = STORE_THROUGH_DEFAULT;
+int g_store_through_taken = 0;   // ssac_store_through_taken: the bits the last merged weight-gradient launch took
 
 // May a launch of the lean kernel with four K-groups and the Adam epilogue (p filled in by launch_pair_ks) take the
 // fixed-shape form?  Everything wgrad_fixed_kernel compiles in as a constant or leaves out is checked here.
@@ -1529,9 +1556,13 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
         const size_t lds_fixed = lds + sizeof(float) * FX_WSUM;
         if (lean && g_wgrad_fixed && lds_fixed <= PAIR_LDS_MAX && wgrad_fixed_ok(p, batch0, total)) {
             static bool raised_fixed = false;
-            if (ssac_raise_lds(raised_fixed, PAIR_LDS_MAX, "wgrad_fixed", wgrad_fixed_kernel)) return 1;
-            SSAC_LAUNCH(wgrad_fixed_kernel, dim3(total), dim3(NTHREADS * KS), lds_fixed, st, wgrad_fixed_args(p));
+            const void *fx[2] = {(const void *)wgrad_fixed_kernel<false>, (const void *)wgrad_fixed_kernel<true>};
+            if (ssac_raise_lds(raised_fixed, fx, 2, PAIR_LDS_MAX, "wgrad_fixed")) return 1;
+            // (write-through optimizer stores of the fc2 tiles: wgrad_fixed_ok has checked the 16-byte form of all four arenas)
+            const bool wt = (g_store_through & STORE_THROUGH_WGRAD) != 0;
+            SSAC_LAUNCH(wt ? wgrad_fixed_kernel<true> : wgrad_fixed_kernel<false>, dim3(total), dim3(NTHREADS * KS), lds_fixed, st, wgrad_fixed_args(p));
             g_wgrad_fixed_taken = 1;
+            g_store_through_taken = wt ? STORE_THROUGH_WGRAD : 0;
             return ssac_check_launch("wgrad_fixed");
         }
     }
@@ -1672,6 +1703,13 @@ extern "C" int ssac_wgrad_fixed(int on) {
     return 0;
 }
 extern "C" int ssac_wgrad_fixed_taken(void) { return g_wgrad_fixed_taken; }
+
+extern "C" int ssac_store_through(int mask) {
+    if (mask < -1 || mask > STORE_THROUGH_WGRAD) return ssac_fail("ssac_store_through: 0, 1 (bit 0: the fixed weight-gradient form's optimizer stores) or -1 (the library's default)");
+    g_store_through = mask < 0 ? STORE_THROUGH_DEFAULT : mask;
+    return 0;
+}
+extern "C" int ssac_store_through_taken(void) { return g_store_through_taken; }
 
 extern "C" int64_t ssac_mlp_layout(int in_dim, int hidden, int out_dim, int64_t off[6]) {
     int64_t o = 0;
@@ -1841,6 +1879,7 @@ static int wgrad_merged(const ssac_mlp *nets, const int32_t *net_ids, int n_sel,
     if (!grads && (!adam_m || !adam_v || !ctl)) return ssac_fail("ssac_mlp_wgrad_fc12: Adam state missing");
     if (n_sel == 0 || n_rows <= 0) return 0;
     g_wgrad_fixed_taken = 0;   // (launch_pair_ks says otherwise)
+    g_store_through_taken = 0;
     const int H = nets->hidden;
     GemmPair p{};
     int64_t off[6];

@@ -227,6 +227,32 @@ __device__ __forceinline__ ShiftAxis drqv2_shift_axis(int i, int64_t shift, int 
 // The waitcnt pass still inserts the vmcnt wait in front of the first USE of a loaded register.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// WRITE-THROUGH window of one workgroup on an array that NO workgroup of the same launch loads back (profiles/
+// store_through.md lists the readers per kernel): 16-byte stores that leave the XCD's L2 when they are issued and drop their
+// line (buffer_store_dwordx4 ... offen sc1), instead of lying dirty in L2 until the kernel's end-of-launch write-back sweeps
+// them out in front of the next launch.  The window is a buffer descriptor over the workgroup's OWN tile: `base` is wave-
+// uniform (made provably so here), `bytes` covers exactly what the tile may write -- a store whose byte offset lies at or
+// beyond it is dropped by the descriptor's range check -- and the per-lane offset is a small 32-bit number.  The compiler
+// counts these stores like any other (vmcnt), so nothing is hidden from it.  16-byte stores only: a dword `sc1` store costs
+// about six times as much per byte.  User: the fc2 tiles of the fixed-shape weight-gradient launch (ssac_gemm.hip).
+struct StoreThrough {
+    __amdgpu_buffer_rsrc_t r;
+    __device__ __forceinline__ void init(const float *base, uint32_t bytes) {
+        // (readfirstlane returns a SIGNED int: each half goes through uint32_t, see DirectW::init in ssac_fused.hip)
+        const uint64_t ub = (uint64_t)(uintptr_t)base;
+        const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
+        const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32));
+        r = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)(((uint64_t)bhi << 32) | (uint64_t)blo), 0,
+                                              (int)(uint32_t)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+    }
+    template <typename V4>   // 16 bytes of payload at byte offset `off` (a multiple of 16) of the window
+    __device__ __forceinline__ void store16(uint32_t off, const V4 &v) const {
+        typedef unsigned u4_ __attribute__((ext_vector_type(4)));
+        static_assert(sizeof(V4) == 16, "one dwordx4");
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_, v), r, (int)off, 0, 16);   // aux 16 = sc1
+    }
+};
+
 __device__ __forceinline__ int ssac_xcd_contiguous(int bid, int nwg, int on) {
     if (!on) return bid;
     const int xcd = bid & 7, slot = bid >> 3, q = nwg >> 3, r = nwg & 7;
