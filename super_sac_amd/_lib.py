@@ -304,6 +304,8 @@ TEST_SIGNATURES = {
     "ssac_wgrad_fixed_taken": [],
     "ssac_store_through": [_I],
     "ssac_store_through_taken": [],
+    "ssac_wgrad_state_early": [_I],
+    "ssac_wgrad_state_early_taken": [],
     "ssac_bf16_fwd_form": [_I],
 }
 # include/ssac_hip_test.h, group 2 (lab hooks): defined by the LAB build only (`./build.sh --lab`, SSAC_LAB_BUILD=1); bound when present
