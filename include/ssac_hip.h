@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 16
+#define SSAC_ABI_VERSION 17
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {

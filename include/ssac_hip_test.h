@@ -64,24 +64,6 @@ int ssac_chain_lean_taken(void);
 int ssac_wgrad_fixed(int on);
 /* which form the LAST merged weight-gradient launch took: 1 fixed-shape, 0 any other, -1 no launch yet. */
 int ssac_wgrad_fixed_taken(void);
-/* Write-through (16-byte `sc1`) stores for arrays that one update launch hands to the next and that no workgroup of the
- * writing launch loads back (profiles/store_through.md).  Bit mask, default 1, -1 = the library's default:
- *   bit 0  p, m, v and the Polyak target of the fc2 tiles of the fixed-shape weight-gradient launch (ssac_wgrad_fixed).
- * Everything else keeps plain stores: the fc1 tiles' dword epilogue, the biases, the head workgroups, every other form of the
- * launch.  Cache policy only: bit-identical results. */
-int ssac_store_through(int mask);
-/* the bits the LAST merged weight-gradient launch actually took (0: it was not the fixed form, or the switch was off) */
-int ssac_store_through_taken(void);
-/* When the tiles of the fixed-shape weight-gradient launch (ssac_wgrad_fixed) request their optimizer state
- * (profiles/wgrad_state.md).  Bit mask, default 1, -1 = the library's default:
- *   bit 0  tiles on the 16-byte optimizer form -- every fc2 tile, an fc1 tile of an input width that is a multiple of 4 --
- *          issue no L2 touches at their front and request p / m / v / target one K iteration early, in the K loop's last trip,
- *          into the operand staging registers; 0 = touches at the front and the request in the last chunk.
- * (The same for the dword epilogue of fc1 tiles of other widths measured no gain and has no bit.)  Loads move, nothing else:
- * bit-identical results (tests/test_hip_wgrad_state_early.py). */
-int ssac_wgrad_state_early(int mask);
-/* the bits the LAST merged weight-gradient launch actually took (0: it was not the fixed form, or the switch was off) */
-int ssac_wgrad_state_early_taken(void);
 /* large-batch form of ssac_bf16_mlp3_fwd: 1 (default) = the register-chained kernel where it applies, 0 = the streaming
  * kernel everywhere.  Same operands, same rounding points. */
 int ssac_bf16_fwd_form(int form);

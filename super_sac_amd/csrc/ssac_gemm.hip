@@ -268,17 +268,20 @@ struct LateTau { bool on; uint32_t bits; };
 // so everything derived from them folds at compile time; the flag adds the facts the values alone cannot tell: 1 = an fc2
 // tile (256 x 256: every column block exists, the 16-byte optimizer form, no bias gradient), 2 = an fc1 tile (one column
 // block of at most 32 columns: the waves of the right half never multiply); both: gradient-norm slots are present.
-// WT (fixed form, fc2 tiles): the 16-byte optimizer stores -- p, m, v, target -- leave through write-through windows on the
-// tile's own 64 x 64 block of each arena (StoreThrough, ssac_internal.h).  A tile is the only reader and the only writer of
-// its block in this launch, and it has read it (opt_prefetch) before it stores; the next reader is the next launch.
-// EARLY (fixed form; profiles/wgrad_state.md): a tile on the 16-byte optimizer form -- every fc2 tile, an fc1 tile of a width
-// that is a multiple of 4 -- issues NO L2 touches at its front and requests p / m / v / target ONE K ITERATION EARLIER, in
-// the loop's last trip (chunk iters - 2 multiplies, chunk iters - 1 is staged, no operand load is issued any more): right
-// behind the staging stores and INTO the operand staging registers, which are dead from there on.  Launch-wide the touches
-// were 12.8 MB of dword requests whose only purpose was that the real request would hit in L2; a whole K iteration in front
-// of its use the real request needs no such help.  Same addresses as opt_prefetch; a tile is the only reader and writer of
-// its block in the launch (profiles/store_through.md).
-template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false, int FIXED = 0, bool WT = false, bool EARLY = false>
+// Two more things are the fixed form's alone (both measured against the general kernel's way and kept, both bit for bit
+// what they replaced; the forms they replaced are in the repository's history):
+// * FIXED == 1, write-through (profiles/wgrad_one_form.md leads to the stores' own note): the fc2 tiles' 16-byte optimizer
+//   stores -- p, m, v, target -- leave through write-through windows on the tile's own 64 x 64 block of each arena
+//   (StoreThrough, ssac_internal.h).  A tile is the only reader and the only writer of its block in this launch, and it has
+//   read it (request_early) before it stores; the next reader is the next launch.
+// * FIXED != 0, the early state request (profiles/wgrad_state.md): a tile on the 16-byte optimizer form -- every fc2 tile, an
+//   fc1 tile of a width that is a multiple of 4 -- issues NO L2 touches at its front and requests p / m / v / target ONE K
+//   ITERATION EARLIER than the general kernels do, in the loop's last trip (chunk iters - 2 multiplies, chunk iters - 1 is
+//   staged, no operand load is issued any more): right behind the staging stores and INTO the operand staging registers,
+//   which are dead from there on.  Launch-wide the touches were 12.8 MB of dword requests whose only purpose was that the
+//   real request would hit in L2; a whole K iteration in front of its use the real request needs no such help.  Same
+//   addresses as the general kernels' opt_prefetch.
+template <bool A_KC, bool B_KC, int EPI, int KS, bool VECONLY = false, int FIXED = 0>
 __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int bx, int by, int bz,
                                               float *late_rs, const LossFoldArgs &lf, int lf_mode,
                                               const LogFoldArgs &fold, int &last,
@@ -312,8 +315,9 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     const int e = bz;
     const int m0 = by * BM, n0 = bx * BN;
     static_assert(FIXED == 0 || (VECONLY && EPI == EPI_ADAM && KS == 4), "the fixed-shape form is the lean Adam kernel with four K-groups");
-    static_assert(!WT || FIXED == 1, "write-through optimizer stores: the fixed form's fc2 tiles (whole 64 x 64 blocks, 16-byte form)");
-    static_assert(!EARLY || FIXED != 0, "the early state request: the fixed form (at least two K iterations, four K-groups)");
+    // write-through optimizer stores: the fc2 tiles (whole 64 x 64 blocks, 16-byte form); the early state request: both roles
+    // (at least two K iterations, four K-groups)
+    constexpr bool WT = FIXED == 1, EARLY = FIXED != 0;
     // LEAN_HANDOFF: the fixed form's order of work behind the K loop (profiles/wgrad_handoff.md): partials parked in the
     // free staging buffer with no barrier in front, the optimizer stores issued next, the gradient norm's wave partials
     // (LDS words of their own, one barrier) behind them.  The general kernels keep the hand-off they had.
@@ -396,11 +400,16 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     f4 pf_p, pf_m, pf_v, pf_t;
     ssac_adam_ctl pf_ctl;   // (fixed form: the control block travels with the optimizer state)
     bool pf_done = false;
+    // element (row, col) of the tile: does it exist, and where does it lie in the arenas (16-byte form: thread t owns the 4
+    // consecutive columns from (t >> 4, (t & 15) * 4) on).  (The epilogue's c4[j] spells own_at out: taken through the lambda
+    // there, the same address comes with the operands of one scalar OR swapped in 16 of the gradient / Adam kernels.)
+    auto own_ok = [&](int row, int col) { return (m0 + row) < g.M && (n0 + col) < g.N; };
+    auto own_at = [&](int row, int col) { return coff + (int64_t)(m0 + row) * g.ldc + n0 + col; };
+    // (general kernels)
     auto opt_prefetch = [&]() {
         if (!vecC) return;
         const int row = tid_all >> 4, col = (tid_all & 15) * 4;
-        const bool ok = (m0 + row) < g.M && (n0 + col) < g.N;
-        const int64_t a = ok ? coff + (int64_t)(m0 + row) * g.ldc + n0 + col : coff;
+        const int64_t a = own_ok(row, col) ? own_at(row, col) : coff;
         pf_p = *reinterpret_cast<const f4 *>(g.C + a);
         pf_m = *reinterpret_cast<const f4 *>(g.am + a);
         pf_v = *reinterpret_cast<const f4 *>(g.av + a);
@@ -408,16 +417,15 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         pf_done = true;
     };
 
-    // EARLY: the same request from the K loop's last trip, into the dead staging registers: va.v[0] / va.v[1] / vb.v[0] /
+    // Fixed form: the same request from the K loop's last trip, into the dead staging registers: va.v[0] / va.v[1] / vb.v[0] /
     // vb.v[1] = p / m / v / target (as variables of their own the four would be live beside the staging registers through
     // the loop: the compiler cannot see that the trip that requests them is the last).  The control block stays in the peeled
     // chunk: requested here it comes as vector loads whose results are COPIED into the registers its values hold across the
     // loop, and the copies wait for everything in flight -- a memory latency inside the K loop (profiles/wgrad_state.md).
-    auto state_early = [&]() {
+    auto request_early = [&]() {
         if (vecC) {
             const int row = tid_all >> 4, col = (tid_all & 15) * 4;
-            const bool ok = (m0 + row) < g.M && (n0 + col) < g.N;
-            const int64_t a = ok ? coff + (int64_t)(m0 + row) * g.ldc + n0 + col : coff;
+            const int64_t a = own_ok(row, col) ? own_at(row, col) : coff;
             va.v[0] = *reinterpret_cast<const f4 *>(g.C + a);
             va.v[1] = *reinterpret_cast<const f4 *>(g.am + a);
             vb.v[0] = *reinterpret_cast<const f4 *>(g.av + a);
@@ -434,12 +442,12 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
     // register the compiler did not know to be in flight: correct only as long as the allocator never spilled or
     // re-used that register during the K loop -- the general kernel, at 128 VGPRs with spills, eventually did, and the
     // late-arriving dword overwrote an address: a memory access fault at the metric shape.)
-    // (EARLY: no touches -- the one real request stands a whole K iteration in front of its use)
+    // (fixed form: no touches -- the one real request stands a whole K iteration in front of its use)
     float l2_sink[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (!EARLY && PREFETCH_OPT && vecC) {
         const int row = tid_all >> 4, col = (tid_all & 15) * 4;
-        if ((m0 + row) < g.M && (n0 + col) < g.N) {
-            const int64_t a = coff + (int64_t)(m0 + row) * g.ldc + n0 + col;
+        if (own_ok(row, col)) {
+            const int64_t a = own_at(row, col);
             l2_sink[0] = g.C[a];
             l2_sink[1] = g.am[a];
             l2_sink[2] = g.av[a];
@@ -508,7 +516,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         mm(f0a, f0b);
         storeA(nxt); storeB(nxt + TILE_FLOATS);
         if (it + 2 < iters) { const int k0 = ((it + 2) * KS + kg) * BK; loadA(k0); loadB(k0); }
-        else if constexpr (EARLY) state_early();   // (the last trip: chunk iters - 1 is staged, the registers are dead)
+        else if constexpr (EARLY) request_early();   // (the last trip: chunk iters - 1 is staged, the registers are dead)
         lds_barrier();  // (LDS hand-off only: the loads just issued stay in flight over the next half chunk)
         rd(f0a, f0b, nxt, 0);
         mm(f1a, f1b);
@@ -517,10 +525,9 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
         // last chunk, peeled: nothing is staged any more, so the operand staging registers are dead here and the
         // optimizer state takes their place (inside the loop the two live ranges would have overlapped)
         rd(f1a, f1b, ((iters - 1) & 1) ? buf1 : buf0, 1);
-        if (PREFETCH_OPT && !EARLY) opt_prefetch();
         if constexpr (EARLY) {
             if (vecC) { pf_p = va.v[0]; pf_m = va.v[1]; pf_v = vb.v[0]; pf_t = vb.v[1]; pf_done = true; }
-        }
+        } else if (PREFETCH_OPT) opt_prefetch();
         if constexpr (LEAN_HANDOFF) pf_ctl = *g.ctl;   // (its epilogue no longer opens with work that would hide this load)
         mm(f0a, f0b);
         mm(f1a, f1b);
@@ -618,7 +625,7 @@ __device__ __forceinline__ void ens_gemm_body(const GemmArgs &g, float *lds, int
             for (int j = 0; j < PER4; ++j) {
                 const int id = tid_all + j * NT_ALL;
                 const int row = id >> 4, col = (id & 15) * 4;
-                ok4[j] = (m0 + row) < g.M && (n0 + col) < g.N;
+                ok4[j] = own_ok(row, col);
                 c4[j] = coff + (int64_t)(m0 + row) * g.ldc + n0 + col;
                 if (EPI == EPI_ADAM) {
                     if (PREFETCH_OPT && pf_done) {
@@ -1042,11 +1049,6 @@ __device__ __forceinline__ HeadWgradArgs wgrad_fixed_head(const WgradFixedArgs &
                          p.sumsq2, p.sumsq_stride, p.tw, p.tau, 1, o.b2};
 }
 
-// WT: the fc2 tiles write their optimizer state through (ens_gemm_body, WT) -- what a launch takes; <false> keeps plain stores
-// (ssac_store_through(0)).  One kernel per form, since a kernel holds one instantiation of the body per role.
-// EARLY: tiles on the 16-byte optimizer form request their state one K iteration early and issue no L2 touches (ens_gemm_body,
-// EARLY; ssac_wgrad_state_early(0) keeps <.., false>).
-template <bool WT, bool EARLY>
 __global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArgs p) {
     constexpr int KS = 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1086,12 +1088,12 @@ __global__ __launch_bounds__(NTHREADS * 4) void wgrad_fixed_kernel(WgradFixedArg
     } else if (bid < p.tiles0) {
         const GemmArgs g = wgrad_fixed_tile<1>(p);
         const int bz = bid / FX_TILES2, rem = bid % FX_TILES2;
-        ens_gemm_body<false, false, EPI_ADAM, KS, true, 1, WT, EARLY>(g, lds, rem % FX_GRID, rem / FX_GRID, bz, tab, p.lf, 1, p.fold, last, lt);
+        ens_gemm_body<false, false, EPI_ADAM, KS, true, 1>(g, lds, rem % FX_GRID, rem / FX_GRID, bz, tab, p.lf, 1, p.fold, last, lt);
         drawn = true;
     } else {
         const GemmArgs g = wgrad_fixed_tile<2>(p);
         const int L = bid - p.tiles0;
-        ens_gemm_body<false, false, EPI_ADAM, KS, true, 2, false, EARLY>(g, lds, 0, L % FX_GRID, L / FX_GRID, tab, p.lf, 1, p.fold, last, lt);
+        ens_gemm_body<false, false, EPI_ADAM, KS, true, 2>(g, lds, 0, L % FX_GRID, L / FX_GRID, tab, p.lf, 1, p.fold, last, lt);
         drawn = true;
     }
     if (p.fold.done) {
@@ -1508,17 +1510,6 @@ bool lean_ok(const GemmArgs &g) {
 
 int g_wgrad_fixed = 1;          // ssac_wgrad_fixed: 0 = the merged launch never takes its fixed-shape form
 int g_wgrad_fixed_taken = -1;   // ssac_wgrad_fixed_taken: form of the last merged weight-gradient launch (1 fixed, 0 any other, -1 none yet)
-// ssac_store_through: bit 0 = the fixed form's fc2 tiles write p / m / v / target through (wgrad_fixed_kernel<true>).  On:
-// 47.09 -> 46.04 us per update on the headline, all of it in this launch (profiles/store_through.md; the same stores for
-// h1 / h2 / dz1u of the chained launch's critic tiles measured SLOWER and are not in the library).
-constexpr int STORE_THROUGH_WGRAD = 1, STORE_THROUGH_DEFAULT = STORE_THROUGH_WGRAD;
-int g_store_through = STORE_THROUGH_DEFAULT;
-int g_store_through_taken = 0;   // ssac_store_through_taken: the bits the last merged weight-gradient launch took
-// ssac_wgrad_state_early: bit 0 = the fixed form's tiles on the 16-byte optimizer form request their state one K iteration
-// early and issue no L2 touches (wgrad_fixed_kernel<.., true>; profiles/wgrad_state.md)
-constexpr int STATE_EARLY_16 = 1, STATE_EARLY_DEFAULT = STATE_EARLY_16;
-int g_state_early = STATE_EARLY_DEFAULT;
-int g_state_early_taken = 0;   // ssac_wgrad_state_early_taken: the bits the last merged weight-gradient launch took
 
 // May a launch of the lean kernel with four K-groups and the Adam epilogue (p filled in by launch_pair_ks) take the
 // fixed-shape form?  Everything wgrad_fixed_kernel compiles in as a constant or leaves out is checked here.
@@ -1594,17 +1585,10 @@ int launch_pair_ks(GemmPair &p, int batch0, int batch1, hipStream_t st) {
         const size_t lds_fixed = lds + sizeof(float) * FX_WSUM;
         if (lean && g_wgrad_fixed && lds_fixed <= PAIR_LDS_MAX && wgrad_fixed_ok(p, batch0, total)) {
             static bool raised_fixed = false;
-            // (one kernel per form of the two switches: [write-through stores][early state request])
-            void (*const fx[2][2])(WgradFixedArgs) = {{wgrad_fixed_kernel<false, false>, wgrad_fixed_kernel<false, true>},
-                                                       {wgrad_fixed_kernel<true, false>, wgrad_fixed_kernel<true, true>}};
-            const bool early = (g_state_early & STATE_EARLY_16) != 0;
-            if (ssac_raise_lds(raised_fixed, PAIR_LDS_MAX, "wgrad_fixed", fx[0][0], fx[0][1], fx[1][0], fx[1][1])) return 1;
+            if (ssac_raise_lds(raised_fixed, PAIR_LDS_MAX, "wgrad_fixed", wgrad_fixed_kernel)) return 1;
             // (write-through optimizer stores of the fc2 tiles: wgrad_fixed_ok has checked the 16-byte form of all four arenas)
-            const bool wt = (g_store_through & STORE_THROUGH_WGRAD) != 0;
-            SSAC_LAUNCH(fx[wt][early], dim3(total), dim3(NTHREADS * KS), lds_fixed, st, wgrad_fixed_args(p));
+            SSAC_LAUNCH(wgrad_fixed_kernel, dim3(total), dim3(NTHREADS * KS), lds_fixed, st, wgrad_fixed_args(p));
             g_wgrad_fixed_taken = 1;
-            g_store_through_taken = wt ? STORE_THROUGH_WGRAD : 0;
-            g_state_early_taken = early ? STATE_EARLY_16 : 0;
             return ssac_check_launch("wgrad_fixed");
         }
     }
@@ -1745,20 +1729,6 @@ extern "C" int ssac_wgrad_fixed(int on) {
     return 0;
 }
 extern "C" int ssac_wgrad_fixed_taken(void) { return g_wgrad_fixed_taken; }
-
-extern "C" int ssac_store_through(int mask) {
-    if (mask < -1 || mask > STORE_THROUGH_WGRAD) return ssac_fail("ssac_store_through: 0, 1 (bit 0: the fixed weight-gradient form's optimizer stores) or -1 (the library's default)");
-    g_store_through = mask < 0 ? STORE_THROUGH_DEFAULT : mask;
-    return 0;
-}
-extern "C" int ssac_store_through_taken(void) { return g_store_through_taken; }
-
-extern "C" int ssac_wgrad_state_early(int mask) {
-    if (mask < -1 || mask > STATE_EARLY_16) return ssac_fail("ssac_wgrad_state_early: 0, 1 (bit 0: the 16-byte optimizer form of the fixed weight-gradient tiles) or -1 (the library's default)");
-    g_state_early = mask < 0 ? STATE_EARLY_DEFAULT : mask;
-    return 0;
-}
-extern "C" int ssac_wgrad_state_early_taken(void) { return g_state_early_taken; }
 
 extern "C" int64_t ssac_mlp_layout(int in_dim, int hidden, int out_dim, int64_t off[6]) {
     int64_t o = 0;
@@ -1928,8 +1898,6 @@ static int wgrad_merged(const ssac_mlp *nets, const int32_t *net_ids, int n_sel,
     if (!grads && (!adam_m || !adam_v || !ctl)) return ssac_fail("ssac_mlp_wgrad_fc12: Adam state missing");
     if (n_sel == 0 || n_rows <= 0) return 0;
     g_wgrad_fixed_taken = 0;   // (launch_pair_ks says otherwise)
-    g_store_through_taken = 0;
-    g_state_early_taken = 0;
     const int H = nets->hidden;
     GemmPair p{};
     int64_t off[6];

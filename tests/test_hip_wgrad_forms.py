@@ -3,7 +3,7 @@ ssac_mlp_layer_wgrad, ssac_head_wgrad, ssac_linear_wgrad_splitk + ssac_reduce_sl
 float64 references of wgrad_cases.py: bit for bit on grid inputs in BOTH forced forms, under the CPU-derived bound on Gaussian
 inputs with planted rows; the automatic form equals a forced one, the lean kernel equals the general one and the rebuilt dz2u the
 stored one, bit for bit; Adam / Polyak against a float64 Adam built from the control block; sentinels behind every output.
-Inputs, references and tolerances: wgrad_cases.py.  One case id names one entry point."""
+Inputs, references and tolerances: wgrad_cases.py; the launch harness: wgrad_launch.py.  One case id names one entry point."""
 import ctypes as C
 
 import numpy as np
@@ -11,10 +11,9 @@ import pytest
 import torch
 
 import wgrad_cases as wc
+from wgrad_launch import DEV, SENT, Launch, _check_grads, _check_lossfold, _dev, _sent, _tail_ok, switches_restored
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-SENT, TAIL = wc.SENT, wc.TAIL
 
 
 @pytest.fixture(scope="module")
@@ -25,239 +24,8 @@ def ssa():
 
 @pytest.fixture(autouse=True)
 def _forms_restored(ssa):
-    try:
+    with switches_restored(ssa):
         yield
-    finally:
-        ssa._lib.lib.ssac_wgrad_variant(0)
-        ssa._lib.lib.ssac_gemm_lean(1)
-
-
-def _dev(a, lead=0):
-    """device copy of a host array followed by TAIL sentinel words, `lead` floats off the allocation's (16-byte aligned) base"""
-    a = np.ascontiguousarray(a, np.float32).reshape(-1)
-    buf = torch.full((lead + a.size + TAIL,), SENT, device=DEV)
-    buf[lead:lead + a.size] = torch.from_numpy(a).to(DEV)
-    return buf, buf[lead:]
-
-
-def _sent(numel):
-    return torch.full((numel + TAIL,), SENT, device=DEV)
-
-
-def _tail_ok(buf, numel, what):
-    tail = torch.as_tensor(buf)[numel:numel + TAIL].cpu()
-    assert torch.equal(tail, torch.full((TAIL,), SENT)), f"{what}: written past its end"
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
-
-
-class Launch:
-    """the device buffers of one (case, inputs) and the launch of its entry point"""
-
-    def __init__(self, ssa, case, inp, adam=None):
-        self.ssa, self.case, self.inp, self.adam = ssa, case, inp, adam
-        c = case
-        self.ids = wc.sel_ids(c)
-        self.ns = len(self.ids)
-        self.off, self.stride = wc.layout(c["in_dim"], c["H"], c["out"])
-        offs = (C.c_int64 * 6)()
-        assert ssa._lib.lib.ssac_mlp_layout(c["in_dim"], c["H"], c["out"], offs) == self.stride and list(offs) == self.off
-        self.keep, self.pop = {}, None
-        for k in ("H1", "H2", "DZ1", "DZ2", "DQ", "scale", "W3"):
-            if k in inp:
-                self.keep[k] = _dev(inp[k])[1]
-        self.keep["Xbuf"], self.keep["X"] = _dev(inp["X"], lead=4 + c["xoff"])[0], None
-        self.keep["X"] = self.keep["Xbuf"][4 + c["xoff"]:]
-        assert (self.keep["X"].data_ptr() % 16 == 0) == (c["xoff"] == 0)
-        self.ldx = wc.ldx_of(c)
-        self.xs = c["n"] * self.ldx if c["x"] == "pernet" else 0
-        self.ids_dev = torch.tensor(self.ids, dtype=torch.int32, device=DEV) if c["ids"] is not None else None
-        self.tiles = [wc.wgrad_tiles(c, l) for l in range(3)]
-        desc = ssa._lib.MlpDesc(0, self.stride, c["nets"], c["in_dim"], c["H"], c["out"])
-        for l in range(3):
-            want = ssa._lib.lib.ssac_head_wgrad_tiles(C.byref(desc)) if l == 2 and c["out"] <= 16 else None
-            assert ssa._lib.lib.ssac_wgrad_tiles(C.byref(desc), l) == self.tiles[l] and want in (None, self.tiles[l])
-        # a sumsq row: [head slots | GAP | fc2 slots | GAP | fc1 slots | GAP]
-        # (none in the actor launch: its folded gradient norm sums the whole row of sumsq_net_stride slots)
-        gap = 0 if c["entry"] == "actor" else wc.GAP
-        self.ss_off = {2: 0, 1: self.tiles[2] + gap, 0: self.tiles[2] + self.tiles[1] + 2 * gap}
-        self.ss_stride = sum(self.tiles) + 3 * gap
-        if "lf" in inp:
-            lf = inp["lf"]
-            for k in ("Q", "td", "q_t", "logp", "rew", "done", "weight"):
-                if k in lf:
-                    self.keep[k] = _dev(lf[k])[1]
-            self.keep["la"] = _dev(np.array([lf["log_alpha"]]))[1]
-            pa = c["popart"]
-            self.pop = ssa.engine.DeviceStruct(ssa._lib.PopArtState(0.3, 2.0, pa[0], pa[1], 5, 2, 1, 0, 1e-2), torch.device(DEV)) if pa else None
-        if c["entry"] == "actor":
-            g = wc._rng(c, "actor")
-            self.a_parts = g.standard_normal(wc.ACTOR_TILES).astype(np.float32)
-            self.keep["parts"] = _dev(self.a_parts)[1]
-
-    def run(self, variant=0, lean=1, dz2_null=False):
-        ssa, c, inp, k = self.ssa, self.case, self.inp, self.keep
-        lib, st = ssa._lib.lib, ssa.engine.stream()
-        ssa._lib.check(lib.ssac_wgrad_variant(variant))
-        ssa._lib.check(lib.ssac_gemm_lean(lean))
-        n, H, ns, nets = c["n"], c["H"], self.ns, c["nets"]
-        total = nets * self.stride
-        params_buf, params = _dev(inp["params"])
-        out = dict(params=params_buf)
-        ad = self.adam
-        grads = m = v = tgt = ctl = None
-        if ad is None:
-            grads = out["grads"] = _sent(total)
-        else:
-            pad = np.full((nets, self.stride), SENT, np.float32)
-            st_ = wc.adam_state(ad, (nets, self.stride))
-            live = np.zeros((nets, self.stride), bool)
-            live[:, :self.off[5] + c["out"]] = True
-            arrs = [np.where(live, a, pad) for a in st_]
-            m, v = out["m"], out["v"] = _dev(arrs[0])[0], _dev(arrs[1])[0]
-            if ad["target"]:
-                tgt = out["target"] = _dev(arrs[2])[0]
-            f = wc.adam_ctl(ad)
-            cs = ssa._lib.AdamCtl(f["lr"], f["beta1"], f["beta2"], f["eps"], f["wd"], f["step_size"], f["bc2_sqrt"], 1.0, f["step"],
-                                  (C.c_int32 * 3)(0, 0, 0), wc.LR, wc.BETA1, wc.BETA2)
-            ctl = self.ctl = ssa.engine.DeviceStruct(cs, torch.device(DEV))
-        ss = out["sumsq"] = _sent(ns * self.ss_stride)
-        ssp = lambda l: ss.data_ptr() + 4 * self.ss_off[l]
-        desc = ssa._lib.MlpDesc(params.data_ptr(), self.stride, nets, c["in_dim"], H, c["out"])
-        d, ids, X = C.byref(desc), _p(self.ids_dev), k["X"].data_ptr()
-        mp, vp, cp, gp, tp = _p(m), _p(v), ctl.ptr if ctl else 0, _p(grads), _p(tgt)
-        tau = wc.TAU if tgt is not None else 0.0
-        e = c["entry"]
-        if e == "fc12":
-            rc = lib.ssac_mlp_wgrad_fc12(d, ids, ns, X, self.ldx, self.xs, _p(k["H1"]), _p(k["DZ2"]), _p(k["DZ1"]), n, mp, vp, cp, gp,
-                                         ssp(1), ssp(0), self.ss_stride, tp, tau, st)
-        elif e == "all":
-            rc = lib.ssac_mlp_wgrad_all(d, ids, ns, X, self.ldx, self.xs, _p(k["H1"]), _p(k["H2"]), _p(k["DZ2"]), _p(k["DZ1"]),
-                                        _p(k["DQ"]), n, mp, vp, cp, gp, ssp(2), ssp(1), ssp(0), self.ss_stride, tp, tau, st)
-        elif e == "scaled":
-            rc = lib.ssac_mlp_wgrad_all_scaled(d, ids, ns, X, self.ldx, self.xs, _p(k["H1"]), _p(k["H2"]), _p(k["DZ2"]), _p(k["DZ1"]),
-                                               _p(k["scale"]), n, mp, vp, cp, gp, ssp(2), ssp(1), ssp(0), self.ss_stride, tp, tau, st)
-        elif e == "lossfold":
-            lf = inp["lf"]
-            parts, td_out = out["partials"], out["td_out"] = _sent(2 * nets), _sent(n)
-            spec = None
-            if "q_t" in lf:
-                spec = self.spec = ssa._lib.TdSpec(_p(k["q_t"]), _p(k["logp"]), _p(k["rew"]), _p(k["done"]), _p(k["la"]),
-                                                   td_out.data_ptr(), float(lf["gamma"]), 2, 1, 0)
-            rc = lib.ssac_mlp_wgrad_all_lossfold(
-                d, X, self.ldx, self.xs, _p(k["H1"]), _p(k["H2"]), 0 if dz2_null else _p(k["DZ2"]), _p(k["DZ1"]), _p(k["W3"]),
-                _p(k["Q"]), _p(k.get("td")), C.addressof(spec) if spec else 0, _p(k.get("weight")), self.pop.ptr if self.pop else 0,
-                1 if self.pop else 0, float(c["denom"]), parts.data_ptr(), n, mp, vp, cp, gp, ssp(2), ssp(1), ssp(0),
-                self.ss_stride, tp, tau, 0, st)
-        elif e == "actor":
-            done = out["done"] = torch.zeros(1 + TAIL, dtype=torch.int32, device=DEV)
-            logs = out["logs"] = _dev(np.array([0.75, 0.0]))[0]
-            fold = self.fold = ssa._lib.ActorLogFold(done.data_ptr(), _p(k["parts"]), wc.ACTOR_TILES, n, wc.ACTOR_INV, 0,
-                                                     logs.data_ptr(), logs.data_ptr() + 4, 0, 0, 0)
-            rc = lib.ssac_mlp_wgrad_all_actor(d, X, self.ldx, _p(k["H1"]), _p(k["H2"]), _p(k["DZ2"]), _p(k["DZ1"]), _p(k["DQ"]), n,
-                                              mp, vp, cp, ssp(2), ssp(1), ssp(0), self.ss_stride, C.byref(fold), st)
-        elif e.startswith("layer"):
-            l = int(e[5])
-            Xl, ld, xs = ((X, self.ldx, self.xs), (_p(k["H1"]), H, n * H), (_p(k["H2"]), H, n * H))[l]
-            dY, w = ((k["DZ1"], H), (k["DZ2"], H), (k["DQ"], c["out"]))[l]
-            rc = lib.ssac_mlp_layer_wgrad(d, l, ids, ns, Xl, ld, xs, _p(dY), w, n * w, n, mp, vp, cp, gp, ssp(l), self.ss_stride, tp,
-                                          tau, st)
-        else:
-            assert e == "head"
-            rc = lib.ssac_head_wgrad(d, ids, ns, _p(k["H2"]), _p(k["DQ"]), n, mp, vp, cp, gp, ssp(2), self.ss_stride, tp, tau, st)
-        ssa._lib.check(rc)
-        torch.cuda.synchronize()
-        return {kk: vv.cpu().numpy() for kk, vv in out.items()}
-
-
-    # ---- what the entry point writes
-    def segs(self):
-        e = self.case["entry"]
-        if e == "fc12":
-            return ("w1", "b1", "w2", "b2")
-        if e == "head":
-            return ("w3", "b3")
-        if e.startswith("layer"):
-            l = str(int(e[5]) + 1)
-            return ("w" + l, "b" + l)
-        return wc.SEGS
-
-    def layers(self):
-        return sorted({int(s[1]) - 1 for s in self.segs()})
-
-    def seg_of(self, arena, slot, seg):
-        sl = wc.seg_slices(self.case)[seg]
-        return arena[:self.case["nets"] * self.stride].reshape(self.case["nets"], self.stride)[self.ids[slot], sl].reshape(
-            wc.seg_shapes(self.case)[seg])
-
-    def untouched_ok(self, arena, what, before=None):
-        """every word of the arena outside the written segments of the selected nets: the sentinel (or the value before)"""
-        nets = self.case["nets"]
-        live = np.zeros((nets, self.stride), bool)
-        for s in self.segs():
-            live[self.ids, wc.seg_slices(self.case)[s]] = True
-        a = arena[:nets * self.stride].reshape(nets, self.stride)
-        want = np.full_like(a, SENT) if before is None else np.asarray(before, np.float32).reshape(nets, self.stride)
-        assert np.array_equal(a[~live].view(np.uint32), want[~live].view(np.uint32)), f"{what}: words outside the launch's segments changed"
-        assert np.array_equal(arena[nets * self.stride:], np.full(TAIL, SENT, np.float32)), f"{what}: written past its end"
-
-    def sumsq_rows(self, ss):
-        """per slot and layer the sum over the slots; gaps and tail must hold the sentinel"""
-        rows = ss[:self.ns * self.ss_stride].reshape(self.ns, self.ss_stride)
-        live = np.zeros(self.ss_stride, bool)
-        sums = {}
-        for l in self.layers():
-            live[self.ss_off[l]:self.ss_off[l] + self.tiles[l]] = True
-            sums[l] = rows[:, self.ss_off[l]:self.ss_off[l] + self.tiles[l]].astype(np.float64).sum(1)
-        assert bool((rows[:, ~live] == SENT).all()) and bool((ss[self.ns * self.ss_stride:] == SENT).all()), "sumsq: written outside its slots"
-        assert bool(np.isfinite(rows[:, live]).all()) and bool((rows[:, live] != SENT).all()), "sumsq: a slot of the launch was not written"
-        return sums
-
-
-def _check_grads(L, got, ref, kind, what):
-    c = L.case
-    L.untouched_ok(got["grads"], f"{what}: grads")
-    assert np.array_equal(got["params"][:c["nets"] * L.stride], L.inp["params"].reshape(-1)), f"{what}: gradient store changed the parameters"
-    sums = L.sumsq_rows(got["sumsq"])
-    for slot in range(L.ns):
-        g2 = {l: 0.0 for l in L.layers()}
-        tol = {l: 0.0 for l in L.layers()}
-        for s in L.segs():
-            g, S = ref[s][0][slot], ref[s][1][slot]
-            have = L.seg_of(got["grads"], slot, s).astype(np.float64)
-            d = np.zeros_like(g) if kind == "grid" else wc.bound(s, S)
-            if kind == "grid":
-                assert np.array_equal(have, g.reshape(have.shape)), \
-                    f"{what}: {s} of slot {slot} (net {L.ids[slot]}) differs from the exact sums in {int((have != g.reshape(have.shape)).sum())} elements"
-            else:
-                ratio = np.abs(have - g.reshape(have.shape)) / np.maximum(d.reshape(have.shape), 1e-300)
-                assert float(ratio.max()) <= 1.0, f"{what}: {s} of slot {slot} (net {L.ids[slot]}) off by {float(ratio.max()):.3g} bounds"
-            g2[int(s[1]) - 1] += float((g * g).sum())
-            tol[int(s[1]) - 1] += wc.sumsq_tol(g, d)
-        # per net over ALL slots of the launch: the head workgroups that own fc2's bias gradient (with_b2) add its square to
-        # the head's slots, so only the per-net total is defined
-        have2, want2 = sum(sums[l][slot] for l in L.layers()), sum(g2.values())
-        assert abs(have2 - want2) <= sum(tol.values()), f"{what}: sumsq of slot {slot}: {have2!r} vs {want2!r}"
-
-
-def _check_lossfold(L, got, kind, what):
-    c, inp = L.case, L.inp
-    s = wc.loss_scale(c, inp)
-    _tail_ok(got["partials"], 2 * c["nets"], "partials")
-    _tail_ok(got["td_out"], c["n"], "td_out")
-    parts = got["partials"][:2 * c["nets"]].reshape(c["nets"], 2).astype(np.float64)
-    for e in range(c["nets"]):
-        for j, terms in ((0, s["werr2"][e]), (1, s["err"][e])):
-            if kind == "grid":
-                assert parts[e, j] == terms.sum(), f"{what}: partials[{e}][{j}] on the grid"
-            assert abs(parts[e, j] - terms.sum()) / c["n"] <= wc.log_tol(terms), f"{what}: partials[{e}][{j}] {parts[e, j]!r} vs {terms.sum()!r}"
-    if "q_t" in inp["lf"]:
-        td = got["td_out"][:c["n"]].astype(np.float64)
-        assert bool((np.abs(td - s["td"]) <= (0.0 if kind == "grid" else wc.td_tol(inp["lf"]))).all()), f"{what}: td_out"
-    else:
-        assert bool((got["td_out"] == SENT).all()), f"{what}: td_out written though td was given"
 
 
 def _same(a, b, keys):

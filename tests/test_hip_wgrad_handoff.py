@@ -5,7 +5,7 @@ last chunk -- buffer 0 for an even number of K iterations, buffer 1 for an odd o
 ONE barrier, issues its optimizer stores, and only then reduces the gradient-norm partial (LDS words of its own, one barrier)
 and draws the arrival ticket of the folded logs.  No sum changes its order, so the general kernel's bytes are the reference.
 
-Harness, inputs, float64 references and bounds are those of test_hip_wgrad_fixed.py (zero Adam moments for float64: see there).
+Harness, inputs, float64 references and bounds are those of wgrad_launch.py (zero Adam moments for float64: see there).
 
 Rows.  test_hip_wgrad_fixed.py runs 256 and 384 rows, two and three iterations per K-group.  Here: 512 and 640 rows, four and
 five -- one even and one odd count with more than one trip through the loop's own double buffering behind the first.
@@ -21,9 +21,23 @@ slot stores have drained shows in the folded gradient norm (_check_f64) and in t
 import numpy as np
 import pytest
 
-from test_hip_wgrad_fixed import ADAM, FixedLaunch, _case, _check_f64, _inputs, _same_bytes, ssa, _switches_restored  # noqa: F401
+from wgrad_launch import ADAM, FixedLaunch, _case, _check_f64, _inputs, _same_bytes, switches_restored
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ssa():
+    import super_sac_amd
+    return super_sac_amd
+
+
+@pytest.fixture(autouse=True)
+def _switches_restored(ssa):
+    with switches_restored(ssa):
+        yield
+
+
 SLOT_RTOL = 16 * 2.0 ** -24
 # (dz2u rebuilt, late word, logs): every launch writes parameters, both moments, the target, the slots and the loss partials
 MODES = [(False, None, "none"), (True, 0.25, "folded"), (False, None, "deferred")]

@@ -1,8 +1,7 @@
 """(needs the LAB build of the library: ./build.sh --lab)
 s_memtime phase stamps inside the fp32 chained launch and the merged weight-gradient launch (eager launches of the
-real update at the headline shape; tile 0 of each role)       python tools/fp32_phases.py [B] [N] [fixed] [early]
-fixed: 0 = the weight-gradient launch keeps its general kernel (ssac_wgrad_fixed), default 1
-early: the mask of ssac_wgrad_state_early (0 = the fixed tiles request their optimizer state in the last chunk), default -1"""
+real update at the headline shape; tile 0 of each role)       python tools/fp32_phases.py [B] [N] [fixed]
+fixed: 0 = the weight-gradient launch keeps its general kernel (ssac_wgrad_fixed), default 1"""
 import os, sys
 os.environ.setdefault("SSAC_LAB_BUILD", "1")   # the lab library (./build.sh --lab -> libssac_hip_lab.so)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,8 +16,6 @@ N = int(args[1]) if len(args) > 1 else 10
 ssa.learning.USE_GRAPHS = False
 if len(args) > 2:
     ssa._lib.check(ssa._lib.lib.ssac_wgrad_fixed(int(args[2])))
-if len(args) > 3:
-    ssa._lib.check(ssa._lib.lib.ssac_wgrad_state_early(int(args[3])))
 critic, _ = bc.build(17, 6, B, N, 2)
 for _ in range(5):
     critic()
