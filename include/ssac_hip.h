@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SSAC_ABI_VERSION 17
+#define SSAC_ABI_VERSION 18
 #define SSAC_MAX_NETS 64
 
 typedef struct ssac_mlp {
@@ -271,6 +271,35 @@ int ssac_gather_transition_begin(const void *s, const void *s1, int s_dtype, int
                                  int64_t ld_x, float *x1sa, int64_t ld_x1, float *rew_out, float *done_out,
                                  const ssac_feed *feed, float *logs, int n_logs, ssac_adam_ctl *ctl,
                                  void *stream);
+
+/* The same gather for observations that are SEVERAL vector arrays (a dictionary observation such as
+ * `observation | desired_goal`): the state columns of xsa and x1sa are [key_0 | key_1 | ... | key_{K-1}] in the table's
+ * order, S = the sum of the keys' elems; everything else is ssac_gather_transition's, and with one key the two leave the
+ * same bytes.  Host-side struct, copied into the launch's argument block. */
+#define SSAC_MAX_OBS_KEYS 8
+typedef struct ssac_concat_key {
+    const void *s, *s1;   /* the key's replay arrays (rows x elems) */
+    int32_t dtype;        /* 0 = fp32, 1 = uint8 (cast to fp32) */
+    int32_t _pad;
+    int64_t elems;        /* >= 1 */
+} ssac_concat_key;
+typedef struct ssac_concat {
+    ssac_concat_key key[SSAC_MAX_OBS_KEYS];   /* in column order */
+    int32_t n_keys, _pad;                     /* 1 .. SSAC_MAX_OBS_KEYS */
+} ssac_concat;
+/* idx == NULL: batch row r is source row r (loose tensors laid side by side: an encoder pass without a torch cat); s1 /
+ * x1sa, act, rew / rew_out and done / done_out may then be NULL, and what is NULL is not written.  Refused with an error,
+ * without a launch: n_keys outside 1 .. SSAC_MAX_OBS_KEYS, a NULL source, elems < 1, an unknown dtype, ld_x < S + a_elems,
+ * ld_x1 < S. */
+int ssac_gather_concat(const ssac_concat *table, const float *act, int64_t a_elems, const float *rew,
+                       const uint8_t *done, const int64_t *idx, int n_rows, float *xsa, int64_t ld_x, float *x1sa,
+                       int64_t ld_x1, float *rew_out, float *done_out, void *stream);
+/* ... as the FIRST launch of a captured update, exactly as ssac_gather_transition_begin: indices from the current slot of
+ * feed's ring, and the launch does the work of ssac_begin_update(logs, n_logs, ctl, feed). */
+int ssac_gather_concat_begin(const ssac_concat *table, const float *act, int64_t a_elems, const float *rew,
+                             const uint8_t *done, int n_rows, float *xsa, int64_t ld_x, float *x1sa, int64_t ld_x1,
+                             float *rew_out, float *done_out, const ssac_feed *feed, float *logs, int n_logs,
+                             ssac_adam_ctl *ctl, void *stream);
 
 /* ---- replay push: ReplayBufferStorage.add (replay.py:48-60) for n transitions in ONE launch.  `packed` (device) holds
  * the fields one after the other, each as n rows of row_bytes payload bytes (the result of ONE async host-to-device copy

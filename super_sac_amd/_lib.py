@@ -91,6 +91,19 @@ class Gather(C.Structure):
                 ("rng_word", C.c_int32), ("ctl", C.c_void_p), ("ids_word", C.c_int32), ("_pad", C.c_int32)]
 
 
+class ConcatKey(C.Structure):
+    """struct ssac_concat_key"""
+    _fields_ = [("s", C.c_void_p), ("s1", C.c_void_p), ("dtype", C.c_int32), ("_pad", C.c_int32), ("elems", C.c_int64)]
+
+
+MAX_OBS_KEYS = 8   # SSAC_MAX_OBS_KEYS
+
+
+class Concat(C.Structure):
+    """struct ssac_concat"""
+    _fields_ = [("key", ConcatKey * MAX_OBS_KEYS), ("n_keys", C.c_int32), ("_pad", C.c_int32)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _MP = C.POINTER(MlpDesc)
 
@@ -144,6 +157,8 @@ SIGNATURES = {
     "ssac_target_fwd_critic_bwdu": [_MP, _P, _I, _P, _L, _I, _P, _MP, _P, _P, _P, _L, _P, _P, _P],
     "ssac_gather_transition": [_P, _P, _I, _L, _P, _L, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P],
     "ssac_gather_transition_begin": [_P, _P, _I, _L, _P, _L, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P],
+    "ssac_gather_concat": [_P, _P, _L, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P],
+    "ssac_gather_concat_begin": [_P, _P, _L, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P],
     "ssac_adam_step": [_P, _P, _P, _P, _L, _P, _P],
     "ssac_adam_advance": [_P, _P],
     "ssac_begin_update": [_P, _I, _P, _P, _P],
@@ -320,7 +335,7 @@ _RESTYPES = {"ssac_act_create": C.c_void_p, "ssac_act_obs": C.c_void_p, "ssac_ac
 
 # SSAC_ABI_VERSION of include/ssac_hip.h this binding table was written against (bumped with every signature change:
 # a stale .so called with shifted pointer arguments would corrupt device memory)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 def _load():

@@ -1,6 +1,7 @@
 """The acting path as ONE C call per environment step (agent.py:204-315; csrc/ssac_act.hip).
 
-``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent, of a pixel-encoder agent
+``Agent.forward`` / ``Agent.sample_action`` with a numpy observation of an identity-encoder agent (a concatenating encoder over
+several vector keys counts as one once an update has recognised it: the host lays the row out in the encoder's order), of a pixel-encoder agent
 on uint8 or float32 frames, or of an agent with a two-layer MLP encoder (below), take this path: the first call at a given (rule, num_envs) RECORDS the rule's launches -- every actor's
 forward (+ tanh-normal sample from the engine's Philox stream, in the kernel), SUNRISE's ensemble-Q passes on the stacked
 candidates, the rule's reduction (UCB arg-max / mean of mean actions / categorical draw / arg-max of mean probabilities) and
@@ -69,8 +70,10 @@ class _Plan:
         self.pixel_shape = pixel_shape    # (C, H, W) of an image observation that goes through the pixel encoder, or None
         self.mlp_in = mlp_in              # values per row of an observation that goes through a two-layer MLP encoder, or None
         self.obs_dtype = np.dtype(np.float32 if pixel_shape is None else pixel_dtype)   # what the host writes: uint8 / float32 frames
-        self.key = agent.encoder.ssac_identity_key if pixel_shape is None and mlp_in is None \
+        self.key = getattr(agent.encoder, "ssac_identity_key", None) if pixel_shape is None and mlp_in is None \
             else getattr(agent.encoder, "ssac_obs_key", "obs")
+        # a concatenating encoder's ((key, width), ...): the host lays the row out in that order (act)
+        self.concat = getattr(agent.encoder, "ssac_concat_keys", None) if self.key is None else None
         self.discrete = bool(agent.discrete)
         self.A = agent.act_space_size
         self.out_floats = n if self.discrete else n * self.A
@@ -199,9 +202,13 @@ def _eligible(agent, obs, num_envs, sample, rolling):
     if not (ENABLED and isinstance(obs, dict) and engine.CAPTURE is None):
         return False
     if lu.is_identity(agent.encoder):
-        v = obs.get(agent.encoder.ssac_identity_key)
-        if not isinstance(v, np.ndarray) or v.size != num_envs * agent.encoder.embedding_dim:
-            return False
+        # (a foreign concatenating encoder is recognised by the first update that meets it, learning_utils.ensure_adopted,
+        #  never here: until then its calls take the general path)
+        concat = getattr(agent.encoder, "ssac_concat_keys", None)
+        for key, width in concat or ((agent.encoder.ssac_identity_key, agent.encoder.embedding_dim),):
+            v = obs.get(key)
+            if not isinstance(v, np.ndarray) or v.size != num_envs * width:
+                return False
     elif (rolling and not _rolling_passthrough(agent.encoder)) or \
             (_pixel_obs(agent, obs, num_envs) is None and _mlp_obs(agent, obs, num_envs) is None):
         return False          # (an encoder that overrides its rolling interface keeps state between calls: the general path)
@@ -509,7 +516,11 @@ def act(agent, obs, num_envs, sample, return_dist=False, rolling=False):
             _PLANS.pop(agent, None)
         random.setstate(host_state)
         return None
-    v = np.ascontiguousarray(obs[plan.key], dtype=plan.obs_dtype)
+    if plan.concat is None:
+        v = np.ascontiguousarray(obs[plan.key], dtype=plan.obs_dtype)
+    else:
+        # the row in the encoder's column order, every key converted as the identity plan converts its one key
+        v = np.concatenate([np.ascontiguousarray(obs[k], np.float32).reshape(num_envs, w) for k, w in plan.concat], axis=1)
     rc = lib.ssac_act_run(plan.handle, plan.lists[which], v.ctypes.data, v.nbytes, plan.result.ctypes.data, plan.out_floats,
                           engine.stream())
     if rc:

@@ -9,7 +9,8 @@ The engine needs a handful of things the reference's classes do not carry; ``ado
   popart[i]         the reference layer keeps mu / nu / w / b as plain tensors (popart.py:8-20); it is replaced by
                     the device-resident ``popart.PopArtLayer`` initialised from those values
   encoder           ``ssac_identity_key`` when the encoder returns one of its inputs untouched (the scripts' identity
-                    encoders, experiments/gym/train_gym.py:18-28), found by probing with the first batch
+                    encoders, experiments/gym/train_gym.py:18-28), found by probing with the first batch;
+                    ``ssac_concat_keys`` when it lays several vector inputs side by side (probe_concat)
   adv_estimator     replaced by ``adv_estimator.AdvantageEstimator`` (same call signature, adv_estimator.py:82-90)
   act_space_size    read off the actor head
 
@@ -106,6 +107,60 @@ def probe_identity(encoder, obs_dict):
             encoder.__dict__["ssac_identity_key"] = key
             return key
     return None
+
+
+_CONCAT_PROBE_ROWS = 4
+MAX_CONCAT_KEYS = 8   # SSAC_MAX_OBS_KEYS of include/ssac_hip.h
+
+
+def probe_concat(encoder, obs_dict):
+    """concatenating encoders lay their vector inputs side by side (``torch.cat([o["goal"], o["obs"]], 1)``): remember the
+    order and the widths as ``ssac_concat_keys`` = ((key, width), ...) (cached on the encoder), or None.  Such an encoder
+    has no parameter besides the base class's ``have_at_least_one_param`` and no buffer (a running normaliser must not
+    take in probe rows); `obs_dict` ({key: tensor with a leading batch axis}: only shapes and the device are read) has at
+    least TWO keys (one key handed back is probe_identity's case; one key handed back as a copy keeps the refusal), every
+    one a vector; and on four random rows -- from a LOCAL generator, no global random stream moves -- its output is, bit
+    for bit, the keys' columns in some order that uses every key exactly once.
+    Limitation: the rows are N(0, 1) draws, so arithmetic that is the identity on small finite values -- a clamp at +-10,
+    ``nan_to_num`` -- is not seen, and such an encoder would be taken for a pure concatenation."""
+    cached = getattr(encoder, "ssac_concat_keys", None)
+    if cached is not None:
+        return cached
+    if encoder.__dict__.get("_ssac_concat_probed") or obs_dict is None:
+        return None
+    encoder.__dict__["_ssac_concat_probed"] = True
+    if not isinstance(encoder, torch.nn.Module) or not callable(encoder):
+        return None
+    if any(not n.startswith("have_at_least_one_param.") for n, _ in encoder.named_parameters()):
+        return None
+    if any(True for _ in encoder.buffers()):
+        return None
+    if not 2 <= len(obs_dict) <= MAX_CONCAT_KEYS or any(v.dim() != 2 or v.shape[1] < 1 for v in obs_dict.values()):
+        return None
+    widths = {k: int(v.shape[1]) for k, v in obs_dict.items()}
+    dev = next(iter(obs_dict.values())).device
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(0xC0CA7)
+    probe = {k: torch.randn((_CONCAT_PROBE_ROWS, w), generator=gen, dtype=torch.float32).to(dev) for k, w in widths.items()}
+    was_training = encoder.training
+    try:
+        with torch.no_grad():
+            out = encoder(dict(probe))
+    except Exception:   # noqa: BLE001  (an encoder of another kind may reject vector rows: not a concatenation)
+        return None
+    finally:
+        encoder.train(was_training)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (_CONCAT_PROBE_ROWS, sum(widths.values())):
+        return None
+    order, off, left = [], 0, dict(widths)
+    while left:
+        hit = next((k for k, w in left.items() if torch.equal(out[:, off:off + w], probe[k])), None)
+        if hit is None:
+            return None
+        order.append((hit, left.pop(hit)))
+        off += order[-1][1]
+    encoder.__dict__["ssac_concat_keys"] = tuple(order)
+    return encoder.__dict__["ssac_concat_keys"]
 
 
 # ------------------------------------------------------------------------------------------ augmenters

@@ -625,8 +625,9 @@ def _record(gs, kw, verdict, idx_cpu, ids, in_kernel_noise):
     keys_ = list(st_.s_stack.keys())
     # vector observations in one array: the whole-transition gather is the update's first launch and takes
     # over ssac_begin_update's work (ensemble_size 1: a single gather per update)
-    ctx.defer_begin = (FOLD_BEGIN and agent.ensemble_size == 1 and len(keys_) == 1
-                       and st_.s_stack[keys_[0]].dim() == 2)
+    # (... or several vector arrays gathered side by side for a concatenating encoder: ssac_gather_concat_begin)
+    ctx.defer_begin = (FOLD_BEGIN and agent.ensemble_size == 1
+                       and ((len(keys_) == 1 and st_.s_stack[keys_[0]].dim() == 2) or lu.concat_order(st_) is not None))
     c_arena_ = agent.critics[0].arena(dev)
     if (lu.DEFERRED_LOGS and LAUNCH_MODE == "list" and FOLD_LOGS and _loss_folds(B) and LAZY_TD and ctx.defer_begin
             and not kw["critic_clip"] and kind == "stochastic" and not any(agent.popart) and c_arena_.out_dim == 1):

@@ -502,7 +502,17 @@ def ensure_gathered(bt):
         return
     p, bt.pending = bt.pending, None
     S, A, B = p["S"], p["A"], bt.B
-    if p["begin"] is not None:
+    if p.get("table") is not None:
+        # several vector keys side by side (concat_order): one ssac_gather_concat launch, never folded into the merged one
+        out = (B, bt.xsa.data_ptr(), bt.xsa.stride(0), bt.x1sa.data_ptr(), bt.x1sa.stride(0), bt.r.data_ptr(), bt.d.data_ptr())
+        if p["begin"] is not None:
+            blk, ctl = p["begin"]
+            check(lib.ssac_gather_concat_begin(C.byref(p["table"]), p["act"], A, p["rew"], p["done"], *out, p["feed"],
+                                               blk.data_ptr(), LOG_WIDTH, ctl, engine.stream()))
+        else:
+            check(lib.ssac_gather_concat(C.byref(p["table"]), p["act"], A, p["rew"], p["done"], p["idx"].data_ptr(), *out,
+                                         engine.stream()))
+    elif p["begin"] is not None:
         blk, ctl = p["begin"]
         check(lib.ssac_gather_transition_begin(p["s"], p["s1"], p["dtype"], S, p["act"], A, p["rew"], p["done"], B,
                                                bt.xsa.data_ptr(), S + A, bt.x1sa.data_ptr(), S + A, bt.r.data_ptr(),
@@ -578,10 +588,11 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
     orders = draw_augmentation_orders(augmenter, {k: v.shape[1] for k, v in st.s_stack.items() if v.dim() == 4})
     bt = _Batch()
     bt.B, bt.A, bt.pending = B, A, None
-    vec = len(keys) == 1 and st.s_stack[keys[0]].dim() == 2
+    order = concat_order(st)   # ((key, width), ...) of a buffer whose vector keys travel side by side, else None
+    vec = order is not None or (len(keys) == 1 and st.s_stack[keys[0]].dim() == 2)
     if vec:
-        key = keys[0]
-        S = st.s_stack[key].shape[1]
+        key = keys[0] if order is None else order[0][0]
+        S = st.s_stack[key].shape[1] if order is None else sum(w for _, w in order)
         xsa = torch.empty(B, S + A, device=dev) if _xsa is None else _xsa
         assert tuple(xsa.shape) == (B, S + A) and xsa.stride(1) == 1
         x1sa = torch.empty(B, S + A, device=dev)
@@ -594,10 +605,19 @@ def sample_move_and_augment(buffer, batch_size, augmenter, aug_mix, per=True, _d
         bt.pending = dict(s=src.data_ptr(), s1=st.s1_stack[key].data_ptr(), act=st.action_stack.data_ptr(),
                           rew=st.reward_stack.data_ptr(), done=st.done_stack.data_ptr(), idx=idx, S=S, A=A,
                           begin=begin, feed=cap.feed if begin is not None else 0,
-                          dtype=1 if src.dtype == torch.uint8 else 0)
-        if not (_defer_gather and FOLD_GATHER and src.dtype == torch.float32):
+                          dtype=1 if src.dtype == torch.uint8 else 0,
+                          table=None if order is None else concat_table(st.s_stack, st.s1_stack, order))
+        # (the folded gather, ssac_gather, has one source array: a multi-key row is gathered by a launch of its own)
+        if not (_defer_gather and FOLD_GATHER and src.dtype == torch.float32 and order is None):
             ensure_gathered(bt)
-        o, o1, a = {key: xsa[:, :S]}, {key: x1sa[:, :S]}, xsa[:, S:]
+        if order is None:
+            o, o1 = {key: xsa[:, :S]}, {key: x1sa[:, :S]}
+        else:
+            # the replay dict still carries every key: each a column view of the one row
+            offs = np.cumsum([0] + [w for _, w in order])
+            o = {k: xsa[:, c0:c0 + w] for (k, w), c0 in zip(order, offs)}
+            o1 = {k: x1sa[:, c0:c0 + w] for (k, w), c0 in zip(order, offs)}
+        a = xsa[:, S:]
         bt.S, bt.xsa, bt.x1sa, bt.key, bt.pixel = S, xsa, x1sa, key, False
         assert augmenter.is_identity(), "image augmentations need image observations"
     else:
@@ -680,6 +700,9 @@ def encode(encoder, obs_dict, dst=None, save=False):
     key = getattr(encoder, "ssac_identity_key", None)
     if key is not None:
         return obs_dict[key]
+    ck = getattr(encoder, "ssac_concat_keys", None)
+    if ck is not None:
+        return _concat_rows(ck, obs_dict, dst)
     eng = encoder_base.require_engine(encoder, next(iter(obs_dict.values())).device, obs_dict)
     img = obs_dict[getattr(encoder, "ssac_obs_key", "obs")]
     if dst is None:
@@ -704,7 +727,83 @@ def encode_stacked(encoder, first, second, ws, tag, dev):
 
 
 def is_identity(encoder):
-    return getattr(encoder, "ssac_identity_key", None) is not None
+    """no arithmetic between the observation and the state representation: the encoder hands one key back, or lays
+    several vector keys side by side (ssac_concat_keys: an identity over the wider row)"""
+    return (getattr(encoder, "ssac_identity_key", None) is not None
+            or getattr(encoder, "ssac_concat_keys", None) is not None)
+
+
+def concat_order(storage):
+    """((key, width), ...): the column order in which this replay storage's vector keys are gathered into one row, set
+    at first contact with a concatenating encoder (bind_concat_order); None for every other buffer"""
+    return storage.__dict__.get("ssac_concat_order")
+
+
+def bind_concat_order(buffer, encoder):
+    """first contact of a concatenating encoder with a buffer: its column order becomes the storage's.  The replay dict's
+    tensors are column views of ONE gathered row, so a buffer serves one order: an agent that wants another is refused"""
+    st = getattr(buffer, "_storage", None)
+    want = getattr(encoder, "ssac_concat_keys", None)
+    if st is None or want is None:
+        return
+    have = st.__dict__.get("ssac_concat_order")
+    if have == want:
+        return
+    name = type(encoder).__name__
+    if have is not None:
+        raise NotImplementedError(
+            f"{name}: this replay buffer's keys are already laid out as {[k for k, _ in have]} for another agent, and its "
+            f"batches are column views of that one row; {[k for k, _ in want]} needs a buffer of its own")
+    stored = {k: tuple(v.shape[1:]) for k, v in st.s_stack.items()}
+    if stored != {k: (w,) for k, w in want}:
+        raise NotImplementedError(
+            f"{name}: the encoder concatenates {dict(want)}, the replay buffer holds {stored}: every key of the buffer "
+            "must be a vector the encoder uses exactly once")
+    st.ssac_concat_order = want
+
+
+def concat_table(s_arrays, s1_arrays, order):
+    """the ssac_concat of 2-D fp32 / uint8 arrays {key: tensor} in column order `order` (s1_arrays may be None)"""
+    assert 1 <= len(order) <= _lib.MAX_OBS_KEYS
+    t = _lib.Concat()
+    t.n_keys = len(order)
+    for j, (k, w) in enumerate(order):
+        s = s_arrays[k]
+        assert s.dim() == 2 and s.shape[1] == w and s.is_contiguous() and s.dtype in (torch.float32, torch.uint8)
+        s1 = s1_arrays[k] if s1_arrays is not None else None
+        assert s1 is None or (s1.shape == s.shape and s1.dtype == s.dtype and s1.is_contiguous())
+        t.key[j] = _lib.ConcatKey(s.data_ptr(), 0 if s1 is None else s1.data_ptr(), int(s.dtype == torch.uint8), 0, w)
+    t._keep = (s_arrays, s1_arrays)
+    return t
+
+
+def _concat_rows(order, obs_dict, dst=None):
+    """encode() of a concatenating encoder.  A replay batch's tensors are column views of one gathered row
+    (sample_move_and_augment): when pointers, strides and adjacency say so, the (B, S) strided view of that row -- no
+    launch.  Loose tensors: ONE ssac_gather_concat launch (row r = row r) lays them side by side, into dst[:, :S] when
+    given"""
+    first = obs_dict[order[0][0]]
+    B, S = first.shape[0], sum(w for _, w in order)
+    ld, ptr = first.stride(0), first.data_ptr()
+    views = first.dim() == 2 and ld >= S
+    for k, w in order:
+        t = obs_dict[k]
+        views = (views and t.dim() == 2 and t.shape == (B, w) and t.dtype == torch.float32 and t.stride(1) == 1
+                 and t.stride(0) == ld and t.data_ptr() == ptr)
+        ptr += 4 * w
+    if views:
+        return torch.as_strided(first, (B, S), (ld, 1))
+    rows = {}
+    for k, w in order:
+        t = obs_dict[k].flatten(1)
+        assert t.shape == (B, w), f"observation key {k!r}: expected {w} values per row, got {tuple(t.shape)}"
+        rows[k] = t.contiguous() if t.dtype in (torch.float32, torch.uint8) else t.float().contiguous()
+    out = torch.empty(B, S, device=first.device) if dst is None else dst
+    assert out.stride(1) == 1 and out.shape[0] == B
+    table = concat_table(rows, None, order)
+    check(lib.ssac_gather_concat(C.byref(table), 0, 0, 0, 0, 0, B, out.data_ptr(), out.stride(0), 0, 0, 0, 0,
+                                 engine.stream()))
+    return out[:, :S]
 
 
 def ensure_adopted(agent, buffer=None):
@@ -712,6 +811,7 @@ def ensure_adopted(agent, buffer=None):
     its encoder is an identity map, probing it with one row of the buffer's observations"""
     if agent.__dict__.get("_ssac_adopted") and (buffer is None or agent.encoder.__dict__.get("_ssac_probed")
                                                  or is_identity(agent.encoder)):
+        bind_concat_order(buffer, agent.encoder)   # (a concatenating encoder: the buffer's rows take its column order)
         return
     from . import adopt
     adopt.adopt_agent(agent)
@@ -720,9 +820,10 @@ def ensure_adopted(agent, buffer=None):
     st = getattr(buffer, "_storage", None) if buffer is not None else None
     if st is not None and not is_identity(agent.encoder):
         rows = {k: v[:1].float() for k, v in st.s_stack.items()}
-        if adopt.probe_identity(agent.encoder, rows) is None:
+        if adopt.probe_identity(agent.encoder, rows) is None and adopt.probe_concat(agent.encoder, rows) is None:
             from . import mlp_encoder
             mlp_encoder.find_mlp_encoder(agent.encoder, rows)   # (two-layer MLP encoders: recognised once, here)
+    bind_concat_order(buffer, agent.encoder)
 
 
 def _row_stride(t):

@@ -168,6 +168,27 @@ class IdentityEncoder(Encoder):
         return obs_dict[self.ssac_identity_key]
 
 
+class ConcatEncoder(Encoder):
+    """Several vector observations laid side by side (`observation | desired_goal`, robot state plus object state, ...):
+    ``ConcatEncoder({"observation": 10, "desired_goal": 3})`` embeds a row as its keys' values in ``order`` (default: the
+    order of ``dims``).  No arithmetic: the replay gather writes the row in that layout (ssac_gather_concat) and the update
+    and acting paths treat it as an identity encoder over the wider row."""
+
+    def __init__(self, dims, order=None):
+        super().__init__()
+        order = list(dims) if order is None else list(order)
+        assert sorted(order) == sorted(dims), "order must name every key of dims exactly once"
+        self.ssac_concat_keys = tuple((k, int(dims[k])) for k in order)
+        assert all(w >= 1 for _, w in self.ssac_concat_keys)
+
+    @property
+    def embedding_dim(self):
+        return sum(w for _, w in self.ssac_concat_keys)
+
+    def forward(self, obs_dict):
+        return torch.cat([obs_dict[k].flatten(1) for k, _ in self.ssac_concat_keys], 1)
+
+
 class MlpEncoder(Encoder):
     """A trainable two-layer encoder of one vector (or flattened) observation: flatten -> fc1 -> ReLU -> fc2 -> out_act.
     ``MlpEncoder(dim, 128, dim)`` is the function of the reference's ``--shared_encoder``, ``MlpEncoder((18, 18), 256, 2,
